@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- scored (u,i)+(h,r,t) triples/sec of the KTUP scoring path at d=100 on ml1m-shape synthetic data.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-extras]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One step = one pass of the hot path over one batch resident in HBM: 716,800 (u,i) pairs through the KTUP
@@ -11,9 +11,13 @@ worth of scored rows.  Tables are xavier-uniform + row-normalised like the ctors
 N > 1: one process per GPU, tables replicated (9.7 MB), every rank scores its own shard of rows; the scoring path
 has no exchange step, so there is no data-path collective (weak scaling; value = all ranks' rows / max time).
 
-The JSON line also carries: roofline (dominant kernel = KTUP rec forward, algorithmic bytes / HIP-event time),
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR: after the timed steps, the scores of the last step (what a caller of the scoring path receives)
+are written as DIR/scores_rec.npy and DIR/scores_kg.npy (float32; seeded inputs, the same from run to run).
+--full: the line also carries roofline (dominant kernel = KTUP rec forward, algorithmic bytes / HIP-event time),
 cpu_baseline (the oracle port timed on this box's host cores, rank 0, N=1 only), and -- timed separately, outside
-the K-step region -- the B=512 training step and the all-item Hit@10 evaluation latency.
+the K-step region -- the B=512 training step, the all-item Hit@10 evaluation latency and the N-GPU legs
+(--full --no-extras: the roofline only).
 """
 import argparse
 import json
@@ -1331,10 +1335,15 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)       # a step is ~0.17 ms: 200 steps = 35 ms of timed work
     ap.add_argument('--warmup', type=int, default=50)       # long enough for the clocks to settle
-    ap.add_argument('--no-extras', action='store_true', help='skip cpu_baseline / train-step / eval side measurements')
+    ap.add_argument('--full', action='store_true',
+                    help='also the roofline, the CPU baselines, the side measurements and the N-GPU legs (a plain run times the headline only)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip cpu_baseline / train-step / eval side measurements')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the last step\'s scores as DIR/scores_rec.npy and DIR/scores_kg.npy (float32)')
     ap.add_argument('--only', default=None, choices=['gather_stress', 'gather_stress_rec'],
                     help='profiling hook: run only this side measurement (for a rocprofv3 pass) and print its JSON')
     args = ap.parse_args()
+    extras = args.full and not args.no_extras
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -1382,12 +1391,13 @@ def main():
     kg = L.bind('ktup_score_transh_fwd', D_['E'].data_ptr(), D_['E'].stride(0), D_['R'].data_ptr(), D_['R'].stride(0),
                 D_['Rn'].data_ptr(), D_['Rn'].stride(0), D_['R'].shape[0], D, X['h'].data_ptr(), X['t'].data_ptr(),
                 X['r'].data_ptr(), KG_ROWS, 0, s_kg.data_ptr(), side.cuda_stream)
-    with torch.no_grad():    # the bound launches must agree with the autograd wrappers the models use
-        ref_rec = ops.score_ktup(D_['U'], D_['I'], D_['E'], D_['P'], D_['Pn'], D_['R'], D_['Rn'], i2e_d, X['u'], X['i'], False)
-        ref_kg = ops.score_transh(D_['E'], D_['R'], D_['Rn'], X['h'], X['t'], X['r'], False)
-        prep(); rec(); kg()
-        torch.cuda.synchronize(device)
-        assert torch.equal(ref_rec, s_rec) and torch.equal(ref_kg, s_kg), 'bound launches disagree with ops.*'
+    if args.full:
+        with torch.no_grad():    # the bound launches must agree with the autograd wrappers the models use
+            ref_rec = ops.score_ktup(D_['U'], D_['I'], D_['E'], D_['P'], D_['Pn'], D_['R'], D_['Rn'], i2e_d, X['u'], X['i'], False)
+            ref_kg = ops.score_transh(D_['E'], D_['R'], D_['Rn'], X['h'], X['t'], X['r'], False)
+            prep(); rec(); kg()
+            torch.cuda.synchronize(device)
+            assert torch.equal(ref_rec, s_rec) and torch.equal(ref_kg, s_kg), 'bound launches disagree with ops.*'
 
     def barrier():
         if world > 1:
@@ -1443,21 +1453,26 @@ def main():
         for s in range(args.steps):
             print('ev', s, round(z.elapsed_time(ev[s][0]), 4), round(z.elapsed_time(ev[s][1]), 4), round(z.elapsed_time(evk[s][0]), 4),
                   round(z.elapsed_time(evk[s][1]), 4), file=sys.stderr)
-    ek = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
-    for a_, b_ in ek:                                   # the KG-branch kernel alone, timed after the region on its own stream
-        a_.record(side); kg(); b_.record(side)
-    torch.cuda.synchronize(device)
-    eu = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
-    for a_, b_ in eu:                                   # ... and K6 alone (in the region it shares the chip with K3)
-        a_.record(); rec(); b_.record()
-    torch.cuda.synchronize(device)
-    rec_alone_ms = sum(a.elapsed_time(b) for a, b in eu) / len(eu)
+    if args.dump_outputs:                               # the last timed step's scores, before anything else launches
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        tag = '' if world == 1 else '_rank%d' % rank
+        np.save(os.path.join(args.dump_outputs, 'scores_rec%s.npy' % tag), s_rec.cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, 'scores_kg%s.npy' % tag), s_kg.cpu().numpy().astype(np.float32))
+    if args.full:
+        ek = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
+        for a_, b_ in ek:                               # the KG-branch kernel alone, timed after the region on its own stream
+            a_.record(side); kg(); b_.record(side)
+        torch.cuda.synchronize(device)
+        eu = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
+        for a_, b_ in eu:                               # ... and K6 alone (in the region it shares the chip with K3)
+            a_.record(); rec(); b_.record()
+        torch.cuda.synchronize(device)
+        rec_alone_ms = sum(a.elapsed_time(b) for a, b in eu) / len(eu)
     tmax = torch.tensor([dt], device=device)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
-    rec_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
-    kg_ms = sum(a.elapsed_time(b) for a, b in ek) / len(ek)
     rows = (REC_ROWS + KG_ROWS) * world
     out = {
         'metric': 'scored (u,i)+(h,r,t) triples/sec at d=100 (KTUP forward scoring, ml1m shape)',
@@ -1470,12 +1485,15 @@ def main():
                    'users': NU, 'items': NI, 'entities': NE, 'relations': NR, 'd': D},
         'roofline': None,
     }
-    live = live_hbm_traffic() if (rank == 0 and world == 1 and not args.no_extras) else None
-    out['roofline'] = roofline(rec_ms, kg_ms, step_ms=1e3 * dt / args.steps, live_traffic=live)
-    out['roofline']['ms_per_launch_alone'] = rec_alone_ms
-    out['roofline']['note'] = ('ms_per_launch / achieved: HIP events around K6 inside the timed region, where the KG branch (K3) runs '
-                               'concurrently on a second stream; ms_per_launch_alone: the same launch with the chip to itself')
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full:
+        rec_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
+        kg_ms = sum(a.elapsed_time(b) for a, b in ek) / len(ek)
+        live = live_hbm_traffic() if (rank == 0 and world == 1 and extras) else None
+        out['roofline'] = roofline(rec_ms, kg_ms, step_ms=1e3 * dt / args.steps, live_traffic=live)
+        out['roofline']['ms_per_launch_alone'] = rec_alone_ms
+        out['roofline']['note'] = ('ms_per_launch / achieved: HIP events around K6 inside the timed region, where the KG branch (K3) runs '
+                                   'concurrently on a second stream; ms_per_launch_alone: the same launch with the chip to itself')
+    if rank == 0 and world == 1 and extras:
         keep = {}
         out['eval_all_item_hit10'] = eval_bench(device, keep=keep)   # before the CPU baselines: their OpenMP pools disturb host-side timing
         out['train_step_b512'] = train_step_bench(device)
@@ -1492,9 +1510,9 @@ def main():
         out['eval_ktup_l1'] = eval_ktup_l1_bench(device)
         out['eval_all_item_hit10']['cpu_baseline'] = cpu_eval_baseline(keep['m'], keep['users'], keep['gold'], keep['train'], keep['rows'])
         out['cli_steps_per_s'] = cli_throughput_leg()
-    elif rank == 0:
+    elif args.full and rank == 0:
         out['cpu_baseline'] = None
-    if not args.no_extras:
+    if extras:
         # the N-GPU legs the scoring headline cannot show (it has no exchange step): config 4's data-parallel training step and
         # config 5's row-sharded step, each with its comm / compute split (every rank takes part; rank 0 reports)
         legs = {}

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Randomized LIVE comparison of oracle/cpu_ref.py with the reference itself (build container only: it imports /root/reference).
+"""Randomized LIVE comparison of oracle/cpu_ref.py with the reference itself (needs a checkout of the reference: it imports it).
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/live_check.py [--worlds 6] [--seed 0] [--ref /root/reference]
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/live_check.py --ref <checkout of the reference> [--worlds 6] [--seed 0] [--record F.npz]
 
 The goldens pin the oracle on a fixed toy world; this draws random worlds -- table sizes, widths (incl. widths that are not a
 multiple of 4), batch sizes, weights, index batches, recorded Gumbel uniforms, gold / filter sets -- runs the REFERENCE's
@@ -9,8 +9,9 @@ modules on them (through make_goldens.py's harness-side shims; no reference file
 same inputs, and reports the worst disagreement per family: forward scores (bprmf.py, transE/H/R.py, transUP.py, jTransUP.py),
 all-candidate evaluation matrices (evaluate / evaluateRec / evaluateHead / evaluateTail), the drivers' step losses with every
 table's gradient (utils/loss.py + the loss assembly of the three drivers) and the ranking walks
-(utils/misc.py getRecPerformance / getKGPerformance).  Prints ONE JSON line; tests/test_oracle_live_reference.py runs it where
-/root/reference exists (it cannot exist on the GPU box) and holds the numbers to the goldens' bars."""
+(utils/misc.py getRecPerformance / getKGPerformance).  Prints ONE JSON line.  --record F.npz also writes every oracle call's
+arguments and the reference's answer to it, one world in one or more files (tests/golden/make_live_fixtures.py: reference_worlds_<seed>_<world>_<part>.npz), which
+tests/test_oracle_live_reference.py replays against the oracle and holds to the goldens' bars."""
 import json
 import os
 import sys
@@ -23,23 +24,68 @@ def opt(name, default):
     return argv[argv.index(name) + 1] if name in argv else default
 
 
-WORLDS, SEED, REF = int(opt('--worlds', 6)), int(opt('--seed', 0)), opt('--ref', '/root/reference')
+WORLDS, SEED, REF, RECORD = int(opt('--worlds', 6)), int(opt('--seed', 0)), opt('--ref', None), opt('--record', None)
+if REF is None:
+    raise SystemExit('--ref <checkout of the reference> is required')
 sys.argv = [sys.argv[0], '--ref', REF, '--out', os.devnull]      # make_goldens parses its own command line on import
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))       # repo root: oracle/
 import numpy as np                                               # noqa: E402
 import make_goldens as MG                                        # noqa: E402  (imports the reference + installs shims 1, 2)
 import torch                                                     # noqa: E402
-from oracle import cpu_ref as O                                  # noqa: E402
+from oracle import cpu_ref as _O                                 # noqa: E402
 
 V, npy = MG.V, MG.npy
 worst = {}
+EVENTS, ARRAYS, _KEYS = [], {}, {}       # --record: the oracle calls and the reference's answers, in order
 
 
-def note(family, got, want, rtol=1e-5, atol=1e-6):
-    """Relative excess over the bar |got - want| <= atol + rtol |want| (<= 1 passes), kept per family."""
+def _enc(x):
+    """JSON image of an oracle argument; tensors and arrays go to ARRAYS once per distinct content."""
+    import hashlib
+    if isinstance(x, (torch.Tensor, np.ndarray)):
+        a = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        key = (a.dtype.str, a.shape, hashlib.sha1(np.ascontiguousarray(a).tobytes()).hexdigest())
+        if key not in _KEYS:
+            _KEYS[key] = 'a%d' % len(_KEYS)
+            ARRAYS[_KEYS[key]] = a
+        if isinstance(x, torch.Tensor):
+            return {'tensor': _KEYS[key], 'leaf': bool(x.requires_grad)}
+        return {'array': _KEYS[key]}
+    if isinstance(x, (set, frozenset)):
+        return {'set': sorted(int(v) for v in x)}
+    if isinstance(x, np.integer):
+        return int(x)
+    if isinstance(x, np.floating):
+        return float(x)
+    if x is None or isinstance(x, (bool, int, float, str)):
+        return x
+    raise TypeError('cannot record an argument of type %s' % type(x))
+
+
+class _Oracle:
+    """oracle/cpu_ref.py, with every call's arguments logged under --record."""
+    def __getattr__(self, name):
+        fn = getattr(_O, name)
+        if not RECORD or not callable(fn):
+            return fn
+
+        def call(*a, **kw):
+            EVENTS.append({'call': name, 'args': [_enc(v) for v in a], 'kwargs': {k: _enc(v) for k, v in kw.items()}})
+            return fn(*a, **kw)
+        return call
+
+
+O = _Oracle()
+
+
+def note(family, got, want, rtol=1e-5, atol=1e-6, src='result'):
+    """Relative excess over the bar |got - want| <= atol + rtol |want| (<= 1 passes), kept per family.  `got` is the last oracle
+    call's result (src 'result') or the gradient of its idx-th leaf argument (src ['grad', idx, zero the last row])."""
     got = got.detach().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
     want = np.asarray(want)
+    if RECORD:
+        EVENTS.append({'note': family, 'want': _enc(want)['array'], 'rtol': rtol, 'atol': atol, 'src': src})
     assert got.shape == want.shape, (family, got.shape, want.shape)
     if got.size == 0:
         return
@@ -64,12 +110,13 @@ def step_family(family, m, names, loss_ref, W, loss_oracle, pad_ent=None):
     L.backward()
     note(family + '.loss', L.detach(), npy(loss_ref), rtol=2e-5)
     sd = dict(m.named_parameters())
-    for w, n in zip(W, names):
+    for k, (w, n) in enumerate(zip(W, names)):
         want = sd[n].grad
         got = w.grad if w.grad is not None else torch.zeros_like(w)
         if pad_ent == n:
             got = got.clone(); got[-1].zero_()                   # nn.Embedding's padding row takes no gradient (jTransUP.py:96)
-        note(family + '.grad', got, npy(want) if want is not None else np.zeros(tuple(w.shape), np.float32), rtol=1e-4, atol=1e-6)
+        note(family + '.grad', got, npy(want) if want is not None else np.zeros(tuple(w.shape), np.float32), rtol=1e-4, atol=1e-6,
+             src=['grad', k, pad_ent == n])
 
 
 TUP = ['user_embeddings.weight', 'item_embeddings.weight', 'pref_embeddings.weight', 'pref_norm_embeddings.weight']
@@ -193,9 +240,13 @@ def world(rng, gen, wi):
             topn = int(rng.randint(1, 12))
             a = MG.rmisc.getRecPerformance(row, gold, fliter_samples=filt, topn=topn)
             b = O.rec_performance(row, gold, filt, topn)
+            if RECORD:
+                EVENTS.append({'rank': 'rec', 'want': [[float(x) for x in a[:5]], [int(x) for x in a[5]]]})
             mism += int([float(x) for x in a[:5]] != [float(x) for x in b[:5]] or [int(x) for x in a[5]] != [int(x) for x in b[5]])
             a = MG.rmisc.getKGPerformance(row, gold, fliter_samples=filt, topn=topn)
             b = O.kg_performance(row, gold, filt, topn)
+            if RECORD:
+                EVENTS.append({'rank': 'kg', 'want': [[int(x) for x in part] for part in a]})
             mism += int([[int(x) for x in part] for part in a] != [[int(x) for x in part] for part in b])
     finally:
         np.argsort = real_argsort
@@ -207,6 +258,15 @@ def main():
     gen = torch.Generator().manual_seed(SEED + 1)
     for wi in range(WORLDS):
         world(rng, gen, wi)
+        if RECORD:                                               # per world: <F>_<world>_<part>.npz, parts of <= 800 KB of arrays
+            parts, size = [{'__events__': np.array(json.dumps(EVENTS))}], 0
+            for k, a in ARRAYS.items():
+                if size + a.nbytes > 800 * 1024 and len(parts[-1]) > 1:
+                    parts.append({}); size = 0
+                parts[-1][k] = a; size += a.nbytes
+            for pi, arrs in enumerate(parts):
+                np.savez_compressed(RECORD[:-len('.npz')] + '_%d_%d.npz' % (wi, pi), **arrs)
+            del EVENTS[:]; ARRAYS.clear(); _KEYS.clear()
     print(json.dumps({'worlds': WORLDS, 'seed': SEED, 'worst_excess_over_bar': worst}))
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One seeded scenario over the HOST-side functions of the path's callers, run against either package:
 
-    python tests/golden/live_host.py --pkg /root/reference            # the reference's jTransUP
+    python tests/golden/live_host.py --pkg <checkout of the reference> # the reference's jTransUP
     python tests/golden/live_host.py --pkg joint-kg-recommender_amd   # this build's mirror of the same interface
 
 and printed as one JSON document.  tests/test_cli_dropin_live.py runs both (two subprocesses: the packages share their name) and

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the golden vectors under tests/golden/ by IMPORTING THE REFERENCE (build container only).
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_goldens.py [--ref /root/reference]
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_goldens.py --ref <checkout of the reference>
 
 The reference's Python cannot travel to the GPU box, so what is committed is data only: inputs
 (weights, index batches, recorded Gumbel uniforms, filter/gold sets) and the outputs the reference
@@ -35,7 +35,7 @@ import numpy as np
 sys.dont_write_bytecode = True
 
 ap = argparse.ArgumentParser()
-ap.add_argument('--ref', default='/root/reference')
+ap.add_argument('--ref', required=True)
 ap.add_argument('--out', default=os.path.dirname(os.path.abspath(__file__)))
 ap.add_argument('--only', default='', help="'train_steps': write only the three train_steps*.npz fixtures and their _cond files")
 args = ap.parse_args()

@@ -20,7 +20,7 @@ def _line(stdout):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--no-extras'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--full', '--no-extras'],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _line(r.stdout)
@@ -39,10 +39,27 @@ def test_single_gpu_line():
     assert abs(alg['frac_algorithmic'] - alg['achieved'] / 8000.0) < 1e-9 and rf['step_algorithmic_over_peak'] > 0
 
 
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline only; --dump-outputs writes the last timed step's scores as float32 arrays."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _line(r.stdout)
+    assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'} <= set(out)
+    assert out['steps'] == 3 and out['warmup'] == 1 and out['ms_per_step'] > 0
+    assert abs(out['value'] - out['config']['rows_per_step_per_gpu'] * 1e3 / out['ms_per_step']) <= 1e-6 * out['value']
+    assert 'cpu_baseline' not in out and 'config5_step' not in out
+    for name, n in (('scores_rec', 716800), ('scores_kg', 307200)):
+        a = np.load(os.path.join(str(tmp_path), name + '.npy'))
+        assert a.dtype == np.float32 and a.shape == (n,) and np.isfinite(a).all() and a.std() > 0
+
+
 def test_two_ranks_as_the_driver_launches_them():
     env = dict(os.environ, KTUP_BENCH_BACKEND='gloo', KTUP_BENCH_LEG_STEPS='12')       # (short N-GPU legs: two ranks on one GPU stage every exchange through the host)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-           '--master-port', '29571', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2']
+           '--master-port', '29571', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2',
+           '--full']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out = _line(r.stdout)

@@ -1,21 +1,32 @@
-"""Drop-in check of the command-line surface against the reference ITSELF (build container only: reads /root/reference at run
-time, nothing of it is copied): every flag the reference defines (jTransUP/models/base.py: name, kind, default, enum choices) is
-defined here with the same default, and every `python run_*.py ...` command line of the reference's own shell scripts
-(ktup.sh, transup.sh, transe.sh, ...) parses under this build's registry to the values python-gflags would give it."""
+"""Drop-in check of the command-line surface against the reference, from what tests/golden/make_live_fixtures.py recorded of it
+(tests/golden/reference_surface.json: names and values only, nothing of its code): every flag the reference defines
+(jTransUP/models/base.py: name, kind, default, enum choices) is defined here with the same default, and the argument vector of
+every `python run_*.py ...` command line of the reference's own shell scripts (ktup.sh, transup.sh, transe.sh, ...) parses under
+this build's registry to the values python-gflags would give it."""
 import ast
 import glob
+import json
 import os
 import re
 import shlex
 
 import pytest
 
-REF = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'jTransUP')), reason='the reference is present in the build container only')
+HERE = os.path.dirname(os.path.abspath(__file__))
+SURFACE = os.path.join(HERE, 'golden', 'reference_surface.json')
+HOST = os.path.join(HERE, 'golden', 'reference_host.json')
 
 
-def _reference_flags():
-    tree = ast.parse(open(os.path.join(REF, 'jTransUP', 'models', 'base.py')).read())
+def _recorded(key):
+    with open(SURFACE) as f:
+        return json.load(f)[key]
+
+
+def _reference_flags(ref=None):
+    """name -> (kind, default, enum choices): read from the reference's base.py under `ref` (make_live_fixtures.py), else recorded."""
+    if ref is None:
+        return {name: (kind, default, enum) for name, (kind, default, enum) in _recorded('flags').items()}
+    tree = ast.parse(open(os.path.join(ref, 'jTransUP', 'models', 'base.py')).read())
     out = {}
     for node in ast.walk(tree):
         if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr.startswith('DEFINE_'):
@@ -44,8 +55,13 @@ def test_every_reference_flag_is_defined_with_its_default():
     FLAGS.reset()
 
 
-def _script_command_lines():
-    for path in sorted(glob.glob(os.path.join(REF, '*.sh'))):
+def _script_command_lines(ref=None):
+    """(script, program, argument vector) of every `python run_*.py ...` line of the reference's scripts under `ref`, else recorded."""
+    if ref is None:
+        for script, prog, toks in _recorded('command_lines'):
+            yield script, prog, toks
+        return
+    for path in sorted(glob.glob(os.path.join(ref, '*.sh'))):
         for line in open(path):
             m = re.search(r'python\s+(run_\w+\.py)\s+(.*)$', line.strip())
             if m:
@@ -129,8 +145,11 @@ def test_module_surface_matches_the_reference():
     import inspect
     ours_root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'joint-kg-recommender_amd', 'jTransUP')
     checked = 0
+    recorded = _recorded('modules')
+    assert sorted(recorded) == sorted(IN_SCOPE)
     for mod in IN_SCOPE:
-        rfuncs, rclasses = _surface(os.path.join(REF, 'jTransUP', mod + '.py'))
+        rfuncs = {k: tuple(v) for k, v in recorded[mod]['functions'].items()}
+        rclasses = {c: {k: tuple(v) for k, v in ms.items()} for c, ms in recorded[mod]['classes'].items()}
         ofuncs, oclasses = _surface(os.path.join(ours_root, mod + '.py'))
         for name, (args, ndef, star) in rfuncs.items():
             assert name in ofuncs, (mod, name)
@@ -154,24 +173,23 @@ def test_module_surface_matches_the_reference():
 
 
 def test_host_side_functions_behave_like_the_reference():
-    """tests/golden/live_host.py once against the reference's package and once against this build's (two subprocesses: both are called
-    jTransUP): the loaders on the same synthetic dataset files, the train / eval iterators and negative samplers under the same
-    random.seed (the same draws in the same order), the metric helpers -- equal JSON documents, and the same lines on stdout."""
-    import json
+    """tests/golden/live_host.py against this build's package, and the document it printed against the reference's package
+    (tests/golden/reference_host.json, recorded by make_live_fixtures.py): the loaders on the same synthetic dataset files, the train /
+    eval iterators and negative samplers under the same random.seed (the same draws in the same order), the metric helpers -- equal
+    JSON documents, and the same lines on stdout."""
     import subprocess
     import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    root = os.path.dirname(here)
+    root = os.path.dirname(HERE)
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
     env.pop('PYTHONPATH', None)
-    docs = []
-    for pkg in (REF, os.path.join(root, 'joint-kg-recommender_amd')):
-        out = subprocess.run([sys.executable, os.path.join(here, 'golden', 'live_host.py'), '--pkg', pkg], capture_output=True, text=True,
-                             timeout=120, env=env, cwd=root)
-        assert out.returncode == 0, (pkg, out.stderr[-2000:])
-        docs.append(out.stdout.strip().splitlines())
-    assert docs[0][:-1] == docs[1][:-1]                                   # what the loaders print
-    ref, ours = json.loads(docs[0][-1]), json.loads(docs[1][-1])
+    out = subprocess.run([sys.executable, os.path.join(HERE, 'golden', 'live_host.py'), '--pkg', os.path.join(root, 'joint-kg-recommender_amd')],
+                         capture_output=True, text=True, timeout=120, env=env, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    mine = out.stdout.strip().splitlines()
+    with open(HOST) as f:
+        theirs = json.load(f)['stdout']
+    assert theirs[:-1] == mine[:-1]                                       # what the loaders print
+    ref, ours = json.loads(theirs[-1]), json.loads(mine[-1])
     assert sorted(ref) == sorted(ours) and len(ref) == 45
     for key in ref:
         assert ref[key] == ours[key], key

@@ -1,48 +1,100 @@
-"""The oracle against the reference ITSELF on random worlds (tests/golden/live_check.py): runs only where /root/reference exists
--- the build container -- in a subprocess of its own, because the reference's package and this build's mirror of its interface
-are both called jTransUP.  Skipped on the GPU box, where the reference cannot be (the committed goldens are what travels)."""
+"""The oracle against the reference on random worlds, and the host samplers against the reference's draws -- both from what
+tests/golden/make_live_fixtures.py recorded of the reference (its outputs only): tests/golden/live_check.py --record ran the
+reference's modules and the oracle on the same random worlds and kept every oracle call's arguments with the reference's answer
+(reference_worlds_<seed>_<world>_<part>.npz); here the oracle answers the same calls again and is held to the goldens' bars."""
+import glob
 import json
 import os
-import subprocess
-import sys
 
+import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = '/root/reference'
+WORLDS, WORLD_SEEDS = 5, (0, 1)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, 'jTransUP')), reason='the reference is present in the build container only')
-@pytest.mark.parametrize('seed', [0, 1])
+def replay_worlds(paths):
+    """Every recorded oracle call of one world (its parts: `paths`) once more, each recorded answer of the reference checked against
+    it (live_check.note's bars) -> {'worst_excess_over_bar': {family: worst relative excess, 'ranking.mismatches': n}}."""
+    import torch
+    from oracle import cpu_ref as O
+    z = {}
+    for path in paths:
+        with np.load(path) as part:
+            z.update({k: part[k] for k in part.files})
+    events = json.loads(str(z['__events__']))
+    worst, mism = {}, 0
+    last, leafs, backed = None, [], False
+
+    def dec(v):
+        if isinstance(v, dict) and 'tensor' in v:
+            t = torch.from_numpy(z[v['tensor']].copy())
+            if v['leaf']:
+                t.requires_grad_(True)
+                leafs.append(t)
+            return t
+        if isinstance(v, dict) and 'array' in v:
+            return z[v['array']].copy()
+        if isinstance(v, dict) and 'set' in v:
+            return set(v['set'])
+        return v
+
+    real_argsort = np.argsort
+    for ev in events:
+        if 'call' in ev:
+            leafs, backed = [], False
+            args = [dec(a) for a in ev['args']]
+            kwargs = {k: dec(v) for k, v in ev['kwargs'].items()}
+            if ev['call'] in ('rec_performance', 'kg_performance'):          # the tie rule the build declares (live_check's shim 3)
+                np.argsort = lambda a, *aa, **kw: real_argsort(a, *aa, **dict(kw, kind='stable'))
+            try:
+                last = getattr(O, ev['call'])(*args, **kwargs)
+            finally:
+                np.argsort = real_argsort
+        elif 'note' in ev:
+            if ev['src'] == 'result':
+                got = last
+            else:
+                _, k, zero_last = ev['src']
+                if not backed:
+                    last.backward()
+                    backed = True
+                got = leafs[k].grad if leafs[k].grad is not None else torch.zeros_like(leafs[k])
+                if zero_last:
+                    got = got.clone(); got[-1].zero_()
+            got = got.detach().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
+            want = z[ev['want']]
+            assert got.shape == want.shape, (ev['note'], got.shape, want.shape)
+            if got.size:
+                ex = float((np.abs(got.astype(np.float64) - want) / (ev['atol'] + ev['rtol'] * np.abs(want))).max())
+                worst[ev['note']] = max(worst.get(ev['note'], 0.0), ex)
+        elif ev['rank'] == 'rec':
+            mism += int([float(x) for x in last[:5]] != ev['want'][0] or [int(x) for x in last[5]] != ev['want'][1])
+        else:
+            mism += int([[int(x) for x in part] for part in last] != ev['want'])
+    worst['ranking.mismatches'] = mism
+    return {'worst_excess_over_bar': worst}
+
+
+@pytest.mark.parametrize('seed', list(WORLD_SEEDS))
 def test_oracle_matches_the_live_reference_on_random_worlds(seed):
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
-    env.pop('PYTHONPATH', None)
-    out = subprocess.run([sys.executable, os.path.join(HERE, 'golden', 'live_check.py'), '--worlds', '5', '--seed', str(seed), '--ref', REF],
-                         capture_output=True, text=True, timeout=600, env=env, cwd=os.path.dirname(HERE))
-    assert out.returncode == 0, out.stderr[-2000:]
-    rep = json.loads(out.stdout.strip().splitlines()[-1])
-    worst = rep['worst_excess_over_bar']
+    worst = {}
+    for wi in range(WORLDS):
+        parts = sorted(glob.glob(os.path.join(HERE, 'golden', 'reference_worlds_%d_%d_*.npz' % (seed, wi))))
+        assert parts and parts[0].endswith('_0.npz'), (seed, wi)
+        for k, v in replay_worlds(parts)['worst_excess_over_bar'].items():
+            worst[k] = worst.get(k, 0) + v if k == 'ranking.mismatches' else max(worst.get(k, 0.0), v)
     assert worst.pop('ranking.mismatches') == 0
     assert len(worst) == 24                                      # every family ran: scores / evaluation matrices of eight model kinds, step loss + gradients of four
     # 1.0 = the goldens' bars (|diff| <= 1e-6 + 1e-5 |reference|; TransR 1e-5 + 1e-4; gradients 1e-6 + 1e-4)
     assert all(v <= 1.0 for v in worst.values()), worst
 
 
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REF, 'jTransUP', 'utils', 'data.py')), reason='the reference is present in the build container only')
-def test_host_samplers_draw_what_the_reference_draws():
-    """jTransUP/utils/data.py keeps the per-user union of the rating dicts between batches and slices the epoch's order as an array
-    (the reference rebuilds the union per rating: 5.6 -> 0.7 ms per batch of 512): under the same `random` seed the negatives, the
-    corrupted triples and the batches are the reference's, draw for draw.  The reference's module is loaded by path (it imports
-    random, copy and numpy only)."""
-    import importlib.util
+def sampler_draws(mod):
+    """The host samplers' draws under random.seed(11) on a seeded toy world: batches of ratings with their negatives, corrupted
+    triples, over several epochs and two sets of rating dicts.  `mod`: a module with the interface of jTransUP/utils/data.py."""
     import random
-    import sys as _sys
     import numpy as np
-    spec = importlib.util.spec_from_file_location('ktup_reference_utils_data', os.path.join(REF, 'jTransUP', 'utils', 'data.py'))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    _sys.path.insert(0, os.path.join(os.path.dirname(HERE), 'joint-kg-recommender_amd'))
-    from jTransUP.utils import data as mine
     rng = np.random.RandomState(3)
     NU, NI, NE, NR = 120, 90, 200, 7
     splits = [{u: set(rng.randint(0, NI, rng.randint(1, 25)).tolist()) for u in range(NU) if rng.rand() < p} for p in (1.0, 0.6, 0.5)]
@@ -51,20 +103,38 @@ def test_host_samplers_draw_what_the_reference_draws():
     hd, td = {}, {}
     for h, t, r in triples:
         hd.setdefault((t, r), set()).add(h); td.setdefault((h, r), set()).add(t)
+    random.seed(11)
+    out = []
+    it = mod.MakeTrainIterator(ratings, 64)
+    it2 = mod.MakeTrainIterator(triples, 48, negtive_samples=2)
+    for _ in range(3 * (len(ratings) // 64) + 2):                       # several epochs: the order is reshuffled, users recur
+        out.append(mod.getNegRatings(next(it), NI, all_dicts=splits))
+    for _ in range(2 * (2 * len(triples) // 48) + 2):
+        batch = [tuple(x) for x in next(it2)]
+        out.append(mod.getTrainTripleBatch(batch, NE, all_head_dicts=[hd], all_tail_dicts=[td]))
+    out.append(mod.getNegRatings(ratings[:40], NI, all_dicts=splits[:2]))     # another set of dicts: another cache entry
+    out.append(mod.getNegRatings(ratings[:40], NI, all_dicts=splits))
+    return out
 
-    def run(mod):
-        random.seed(11)
-        out = []
-        it = mod.MakeTrainIterator(ratings, 64)
-        it2 = mod.MakeTrainIterator(triples, 48, negtive_samples=2)
-        for _ in range(3 * (len(ratings) // 64) + 2):                       # several epochs: the order is reshuffled, users recur
-            out.append(mod.getNegRatings(next(it), NI, all_dicts=splits))
-        for _ in range(2 * (2 * len(triples) // 48) + 2):
-            batch = [tuple(x) for x in next(it2)]
-            out.append(mod.getTrainTripleBatch(batch, NE, all_head_dicts=[hd], all_tail_dicts=[td]))
-        out.append(mod.getNegRatings(ratings[:40], NI, all_dicts=splits[:2]))     # another set of dicts: another cache entry
-        out.append(mod.getNegRatings(ratings[:40], NI, all_dicts=splits))
-        return out
 
-    assert run(mine) == run(ref)
-    assert run(mine) == run(ref)                                            # and again, with the unions already cached
+def plain_draws(out):
+    """JSON image of sampler_draws' result (tuples -> lists, numpy ints -> ints)."""
+    if isinstance(out, np.ndarray):
+        out = out.tolist()
+    if isinstance(out, (list, tuple)):
+        return [plain_draws(x) for x in out]
+    return int(out) if hasattr(out, '__index__') else out
+
+
+def test_host_samplers_draw_what_the_reference_draws():
+    """jTransUP/utils/data.py keeps the per-user union of the rating dicts between batches and slices the epoch's order as an array
+    (the reference rebuilds the union per rating: 5.6 -> 0.7 ms per batch of 512): under the same `random` seed the negatives, the
+    corrupted triples and the batches are the reference's, draw for draw -- the reference's draws recorded by
+    tests/golden/make_live_fixtures.py (tests/golden/reference_samplers.json)."""
+    import sys as _sys
+    _sys.path.insert(0, os.path.join(os.path.dirname(HERE), 'joint-kg-recommender_amd'))
+    from jTransUP.utils import data as mine
+    with open(os.path.join(HERE, 'golden', 'reference_samplers.json')) as f:
+        ref = json.load(f)['draws']
+    assert plain_draws(sampler_draws(mine)) == ref
+    assert plain_draws(sampler_draws(mine)) == ref                       # and again, with the unions already cached

@@ -64,7 +64,7 @@ rm -rf /tmp/kp_fwd256
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kp_fwd256 -- python $R/tools/fwd_d256_time.py > /dev/null 2>&1)
 F=$(find /tmp/kp_fwd256 -name "*kernel_stats.csv" | head -1)
 [ -n "$F" ] && cp $F $P/${TAG}_fwd_d256_kernel_stats.csv
-timeout 900 python bench.py > $P/${TAG}_bench.json 2>/dev/null
+timeout 900 python bench.py --full > $P/${TAG}_bench.json 2>/dev/null
 # the numbers a reader is shown come from the files themselves; the stamp ties them to the kernel sources they were measured on
 python tools/profile_summary.py $TAG $P
 ls -la $P

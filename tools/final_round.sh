@@ -9,7 +9,7 @@ mkdir -p $P
 timeout 500 python -m pytest tests -m gpu -x -q > $R/gpurun_out/${TAG}_gpu_tests.txt 2>&1
 grep -E "passed|failed|rror" $R/gpurun_out/${TAG}_gpu_tests.txt | tail -3
 (python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | grep -i "smoke\|error" | tail -3)
-timeout 600 python bench.py > $P/${TAG}_bench.json 2> $R/gpurun_out/${TAG}_bench.err
+timeout 600 python bench.py --full > $P/${TAG}_bench.json 2> $P/${TAG}_bench.err
 for W in kg_pass_e_l1 kg_pass_l1 soft_l1_pass; do
   rm -rf /tmp/kp_$W
   (cd /tmp && timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kp_$W -- python $R/tools/pmc_workloads.py $W > /dev/null 2>&1)
