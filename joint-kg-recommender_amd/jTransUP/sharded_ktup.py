@@ -37,6 +37,7 @@ capacity_factor = world can never overflow.
 """
 import ctypes
 import math
+import os
 
 import torch
 import torch.distributed as dist
@@ -45,6 +46,16 @@ from jTransUP.hip import lib as L
 
 KINDS = {'sgd': 0, 'adagrad': 1, 'adam': 2}
 SLOTS = 16          # the sum of squares is accumulated in this many words (one atomic per workgroup, ~20 ns each on one address)
+# Switches for profile jobs, read once at import:
+# KTUP_C5_DUP=0: the one-rank norm walk sums the squares of every reduced row itself, instead of the step kernel summing the stored
+# rows' squares and the walk only correcting for the rows that several entries share
+C5_DUP = os.environ.get('KTUP_C5_DUP', '1') != '0'
+# KTUP_EXCHANGE_LAYOUT=<anything but open>: the whole-step graph of the exchange form joins every side branch inside its own segment, as
+# the per-segment graphs do, instead of leaving one branch open across the collectives
+EXCHANGE_OPEN_BRANCH = os.environ.get('KTUP_EXCHANGE_LAYOUT', 'open') == 'open'
+# KTUP_STEP_SMALL_WS=0: the rec step kernel adds the preference tables' gradients to one copy instead of to eight replicas that the
+# next launch folds (ShardedKtupStepper._small_ws)
+STEP_SMALL_WS = os.environ.get('KTUP_STEP_SMALL_WS', '1') != '0'
 
 
 class AdamRule(ctypes.Structure):
@@ -112,8 +123,76 @@ def _i64s(vs):
 
 class _ShardedStepBase(object):
     """What the rec and the kg stepper share: eager warm-up, capture of the segments as HIP graphs, replay, the collectives
-    between the segments, the skipped-step counter.  A subclass provides `_bind(stream, side)` -> list of segments (lists of
-    pre-bound launches; ('fork', [...]) / ('join',) around launches bound to the side stream) and the buffers `_exchange` names."""
+    between the segments, the skipped-step counter, the batch feed -- and `_arrange`, the one place where a launch's position in
+    the step is decided.  A subclass binds its own launches by role (`_launches`), writes the route launch (`_route_launch`) and
+    names its static id buffers (`_ids`); `_bind(stream, side)` -> list of segments (lists of pre-bound launches, with
+    ('beside', main launches, side-stream launches) / ('join',) where a second stream carries a branch)."""
+
+    # ------------------------------------------------------------------------------------------------ construction (both steppers)
+    def _init_rule(self, kind, betas, weight_decay):
+        if kind not in KINDS:
+            raise ValueError('row-sparse steps exist for plain SGD, Adagrad and Adam')
+        self.kind, self.weight_decay = kind, float(weight_decay)
+        self.lazy = is_lazy(kind, weight_decay)
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.has_state = kind != 'sgd' or self.lazy
+
+    def _init_job(self, group, force_exchange, capacity_factor):
+        self.group = group
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        if any(t.world != self.world or t.rank != self.rank for t in self.tables):
+            raise ValueError('the tables must be sharded over the stepper\'s process group')
+        # force_exchange: take the several-ranks route (five segments, the three all-to-alls and the all-reduce) on ONE rank too --
+        # what a rank of a bigger job runs, minus the wire; with an initialised process group the collectives are real (RCCL at
+        # world 1), without one they are device copies
+        self.multi = self.world > 1 or bool(force_exchange)
+        self.capacity_factor = float(capacity_factor)
+
+    def _init_capacity(self, n_dist):
+        """n_dist[t]: entries of table t per step = at most this many DISTINCT ids (the module docstring: fixed capacity)."""
+        Wn = self.world
+        self.cap = [n if Wn == 1 else min(n, int(math.ceil(self.capacity_factor * n / Wn)) + 64) for n in n_dist]
+        self.capsum = sum(self.cap)
+        self.W = Wn * self.capsum
+
+    def _init_run(self, use_graphs, overlap_route, exchange_graph, fused_apply=True, route_beside=False, opt_step=None):
+        """The streams, the graph bookkeeping, the feed state and the step counters -- every field run / run_cycle / _capture read."""
+        self.use_graphs, self.overlap_route, self.exchange_graph = bool(use_graphs), bool(overlap_route), bool(exchange_graph)
+        # fused_apply: reduce -> norm -> apply as two walks over the per-pair gradients (no W x d gradient buffer in between);
+        # False keeps the three-launch form through Gwire (same results to rounding: the tests run both)
+        self.fused_apply, self.route_beside, self.pipeline_route = bool(fused_apply), bool(route_beside), True
+        self._side = torch.cuda.Stream(device=self.dev) if self.overlap_route else None
+        self.cursor = torch.zeros(1, dtype=torch.int64, device=self.dev)  # batch the next step reads (device side, moves by itself)
+        self._feed = tuple(self._ids) + (1,)
+        self._fed = self._routed = False
+        self._par = 0
+        self.skipped = torch.zeros(1, dtype=torch.int32, device=self.dev)     # steps skipped for overflow: never cleared by a launch
+        # Adam: the number of the step being applied, in device memory (the launches are replayed from graphs); shared by the steppers
+        # of a joint schedule.  ktup_shard_step_count moves it just before every apply launch.
+        self.opt_step = opt_step if opt_step is not None else torch.zeros(2, dtype=torch.int64, device=self.dev)  # [step, two floats of bias corrections]
+        self.steps = 0
+        self._eager = None
+        self._graphs = self._graphs1 = self._cycles = None
+
+    def _init_exchange(self, n_bucket):
+        """Several ranks: what the collectives move and what the owner's side of the step works in."""
+        W, d, dev, lib = self.W, self.d, self.dev, L.load()
+        i64 = lambda n, fill: torch.full((n,), fill, dtype=torch.int64, device=dev)
+        i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+        self.recv_ids = i64(W, -1)
+        self.Xsend = torch.zeros(W, d, dtype=torch.float32, device=dev)
+        self.Grecv = torch.zeros(W, d, dtype=torch.float32, device=dev)
+        self.cap_own = [max(1, min(self.world * c, t.weight.shape[0])) for c, t in zip(self.cap, self.tables)]
+        self.W_own = Wo = sum(self.cap_own)
+        self.own_inverse = i64(W, 0)
+        self.own_ids = i64(Wo, -1)
+        self.own_sort = i32((lib.ktup_shard_route_sort_bytes(W, Wo) + 3) // 4)
+        self.own_counters = i32(len(self.tables) + 1)
+        self.own_ws = torch.empty((lib.ktup_shard_route_workspace_bytes(W) + 7) // 8, dtype=torch.int64, device=dev)
+        self.Gown = torch.zeros(Wo, d, dtype=torch.float32, device=dev)
+        self.own_xkeys = i32(max(2, lib.ktup_shard_reduce_list_len(W, d)))
+        self.bucket = torch.zeros(n_bucket + 2, dtype=torch.float64, device=dev)   # [small gradients | sum of squares | overflow flag]
 
     def _exchange(self, k):
         """The collective after segment k (several ranks only)."""
@@ -139,7 +218,7 @@ class _ShardedStepBase(object):
         """Several ranks: the five segments AND the collectives between them as ONE graph -- when the collectives can be captured (RCCL, or
         the device copies that stand for them when one rank talks to itself without a process group).  Under gloo (the CPU staging of the
         two-ranks-share-the-GPU tests) every segment stays a graph of its own with the collectives issued between the replays."""
-        if not self.multi or not getattr(self, 'exchange_graph', True):
+        if not self.multi or not self.exchange_graph:
             return False
         return (not dist.is_initialized()) or dist.get_backend(self.group) == 'nccl'
 
@@ -159,7 +238,7 @@ class _ShardedStepBase(object):
         not there yet.)  The first step after set_feed routes itself (run()).  One rank: the walks of step s read the route's output
         to their end, so the route's buffers exist TWICE (`_sets`) and steps alternate between them -- two graphs, `_graphs` and
         `_graphs1`; several ranks: the requester's side of the route is free once the bucket launch has read the overflow word."""
-        return self._fed and getattr(self, 'pipeline_route', True) and not getattr(self, 'route_beside', False)
+        return self._fed and self.pipeline_route and not self.route_beside
 
     def _double(self):
         return self._pipelined()
@@ -170,10 +249,52 @@ class _ShardedStepBase(object):
             setattr(self, k, v)
         self._bind_par = par
 
-    def _open_branch(self):
-        import os
-        return os.environ.get('KTUP_EXCHANGE_LAYOUT', 'open') == 'open'
+    # ------------------------------------------------------------------------------------------------ the batch
+    def load_batch(self, *ids):
+        """Copy a batch (one int64 tensor of B ids per id buffer of the stepper, in the order of its `step(...)` arguments) into the
+        step's static id buffers (skip it by writing the buffers in place, or by set_feed)."""
+        if len(ids) != len(self._ids):
+            raise TypeError('a batch of this stepper is %d id tensors, got %d' % (len(self._ids), len(ids)))
+        if self._feed[0] is not self._ids[0]:
+            self.set_feed(None)
+        for dst, src in zip(self._ids, ids):
+            dst.copy_(src, non_blocking=True)
 
+    def set_feed(self, columns):
+        """Device-fed batches: columns = one contiguous int64 device tensor of n_batches x B ids per id buffer, in load_batch's order (an
+        epoch of pre-drawn batches, or whatever a device-side sampler refills in place).  Step s reads batch (cursor mod n_batches) and
+        the step's own first launches move the device cursor on: `run()` then needs no per-step copy or argument.  None: back to the
+        static one-batch buffers that load_batch fills."""
+        if columns is None:
+            self._feed = tuple(self._ids) + (1,)
+        else:
+            cs = tuple(columns)
+            if len(cs) != len(self._ids):
+                raise L.KtupError('a feed of this stepper is %d columns, got %d' % (len(self._ids), len(cs)))
+            for c in cs:
+                if c.dtype != torch.int64 or c.device != self.dev or not c.is_contiguous() or c.numel() % self.B or c.numel() != cs[0].numel():
+                    raise L.KtupError('feed columns are contiguous int64 device tensors of n_batches x B ids each')
+            self._feed = cs + (cs[0].numel() // self.B,)
+        self._fed, self._routed, self._par = columns is not None, False, 0
+        self.cursor.zero_()
+        self._eager = None
+        self._graphs = self._graphs1 = self._cycles = None                   # the column addresses are baked into the bound launches
+
+    def __call__(self, *ids):
+        if ids:
+            self.load_batch(*ids)
+        self.run()
+
+    def _bind_route(self, stream):
+        keep = []
+        return self._route_launch(4 if self.multi else 0, stream, keep), keep
+
+    def _route(self, phase, on, par=None):
+        """The route's launch (phases: include/ktup_hip.h) on stream `on`, writing buffer set `par` (default: the set in use), for the
+        plan being bound."""
+        return self._route_launch(phase, on, self._keep, par)
+
+    # ------------------------------------------------------------------------------------------------ the step
     def run(self):
         """One step on the ids in the static buffers (or the cursor's batch of the feed columns).  The first two steps issue the
         launches directly (warm-up), then the segments are captured once and replayed."""
@@ -220,7 +341,7 @@ class _ShardedStepBase(object):
         if n <= 0:
             return
         ok = self.use_graphs and not self.multi and self._double() and self.overlap_route and self._routed and self.steps >= 2 and n % 2 == 0 \
-            and getattr(self, 'fused_apply', True)
+            and self.fused_apply
         if not ok:
             for _ in range(n):
                 self.run()
@@ -248,10 +369,6 @@ class _ShardedStepBase(object):
         for item in seg:
             if callable(item):
                 item()
-            elif item[0] == 'fork':                           # launches bound to the side stream, ordered after everything so far
-                side.wait_stream(torch.cuda.current_stream(self.dev))
-                for launch in item[1]:
-                    launch()
             elif item[0] == 'beside':                         # (main launch, side launches): both ordered after everything so far.  The
                 main = torch.cuda.current_stream(self.dev)    # MAIN launch is enqueued first: a captured graph keeps the branch it meets first
                 ev = torch.cuda.Event()                       # on the queue of the launches around it, and the other branch pays the
@@ -295,6 +412,88 @@ class _ShardedStepBase(object):
         else:
             self._graphs, self._graph_keep = graphs, keeps
         return graphs
+
+    # ------------------------------------------------------------------------------------------------ launch lists
+    def _bind(self, stream, side=None):
+        """Pre-bound launches (lib.bind) on `stream` -- and on `side`, a second stream, where a branch runs beside them -- as the
+        segments between the collectives: one segment on one rank, five on several."""
+        keep = self._keep = []                                 # ctypes arrays must outlive the bound launches
+
+        def arr(x):
+            keep.append(x)
+            return ctypes.addressof(x)
+        return self._arrange(self._launches(stream, side, arr), stream, side)
+
+    def _arrange(self, parts, stream, side):
+        """Where every launch of the step sits: `parts` are the subclass's launches by role (`_launches`), the value is the list of
+        segments that `_issue` walks -- callables in the order they are enqueued, ('beside', main, branch) where `branch` (bound to
+        `side`) runs beside `main`, ('join',) where the main stream waits for the branch.
+        parts, one rank: route(phase, stream, par=None) binds the route's launch (phases: include/ktup_hip.h) for buffer set `par`;
+        catchup (lazy rules; else None); pack (None with direct gathers); step (a list: the step kernel and what goes with it);
+        tail (the walks from the stored gradients to the tables; its last launch is the apply walk); beside (the step kernel reads
+        the id columns itself: route_beside).  Several ranks, in addition: sort_, zshared (bound to the branch), rstore,
+        oroute(stream), own_tail (the owner's last two segments)."""
+        route, catch, step = parts['route'], parts.get('catchup'), parts['step']
+        if not self.multi:
+            tail = parts['tail']
+            packed = step if self.direct else [parts['pack']] + step
+            if self._double():     # this step's route ran beside the previous step's walks (into this buffer set); the next step's runs beside these
+                nxt = [route(0, side if side is not None else stream, 1 - self._bind_par)]
+                head = ([catch] if catch else []) + packed
+                # the branch leaves at the step's first launch and is joined in front of its last one: a graph that ENDS in a join pays ~17 us
+                # before the next replay starts (measured), and a route that starts beside the walks ends after them
+                # (joined at the graph's end instead: 0.1217 against 0.1205 ms; the next route on the second stream as a graph of its own with
+                #  events between the replays -- no branch inside the step's graph at all: 0.126; forked after the step kernel, beside the
+                #  walks only: 0.143 -- the branch then ends after the walks and a graph that ends in a late join pays ~17 us)
+                return [[('beside', head + tail[:-1], nxt), ('join',), tail[-1]] if side is not None else head + tail + nxt]
+            if catch:                                        # the whole route, then the catch-up of the rows it named, then whoever reads them
+                return [[route(0, stream), catch] + packed + tail]
+            # one rank, direct gathers, a second stream: the step kernel reads the id columns itself and runs beside the WHOLE route (its
+            # init launch included); its squared norms go to accumulators of their own that the boundary-norm launch folds in, and that
+            # launch moves the cursor once both branches are done
+            # (measured at config 5: 0.151 ms per step against 0.141 with only the route's last four launches beside the kernel -- the init
+            # launch's 1,024 workgroups delay the step kernel's first tiles -- so it is an option, off by default)
+            if parts.get('beside'):
+                return [[('beside', step, [route(3, side)]), ('join',)] + tail]
+            # direct gathers: the step kernel needs only the entry list (the route's first launch), so the rest of the route -- hashing,
+            # slots, the counting sort: four small latency-bound launches -- runs beside it on the second stream
+            if self.direct and side is not None:
+                return [[route(1, stream), ('beside', step, [route(2, side)]), ('join',)] + tail]
+            return [[route(0, stream)] + packed + tail]
+        # ---- several ranks (or one in exchange form): five segments around the three all-to-alls and the all-reduce.  What does not lie on
+        # the path of the data rides on the second stream: the counting sort of the entries (only the gradient reduction reads it) and the
+        # zero-fill of the few wire rows that several entries share run beside the pack launch, the owner's route of the requested rows
+        # (only the owner's reduction reads it) beside the step kernel.  The requester's reduction STORES its rows (ktup_shard_reduce_store):
+        # no zero-filled 42 MB buffer, no read-modify-write.
+        on = side if side is not None else stream
+        pack, sorts, rstore, oroute, own_tail = parts['pack'], [parts['sort_'], parts['zshared']], parts['rstore'], parts['oroute'], list(parts['own_tail'])
+
+        def par(main, beside):
+            return [('beside', main, beside), ('join',)] if side is not None else beside + main
+        whole = side is not None and self._whole_step_graph() and EXCHANGE_OPEN_BRANCH     # one graph: a branch may stay open across the exchanges
+        head, nxt = [route(4, stream)], []
+        if self._pipelined():           # this step's route ran during the previous step (into this buffer set)
+            head, nxt = [], [route(4, on, 1 - self._bind_par)]
+
+        def later(first):
+            """Whole-step graph: the NEXT step's route leaves the main stream at the requester's reduction and is joined after the bucket
+            launch (55 us of main-stream work -- reduction, gradient exchange, norm walk, bucket -- against ~30 of route).  On the branch
+            that carries the sort and the owner's route it ended 23 us after the step kernel and the reduction waited for it
+            (profiles/r06_config5_timeline.txt, first collection)."""
+            if not nxt:
+                return [first]
+            own_tail[0] = own_tail[0] + [('join',)]
+            return [('beside', [first], nxt)]
+        if catch:   # the owner's route of the requested rows moves in front of the pack launch: the catch-up needs its DISTINCT rows
+            if whole:
+                segs = [[oroute(stream), catch, ('beside', [pack], sorts)], step + [('join',)] + later(rstore)]
+            else:
+                segs = [[oroute(stream), catch] + par([pack], sorts), par(step + [rstore], nxt) if nxt else step + [rstore]]
+        elif whole:   # sort, zero-fill, the owner's route (and the next step's route): one branch from the id exchange to the end of the step kernel
+            segs = [[('beside', [pack], sorts + [oroute(on)])], step + [('join',)] + later(rstore)]
+        else:
+            segs = [par([pack], sorts), par(step + [rstore], [oroute(on)] + nxt)]
+        return [head] + segs + own_tail
 
     def _catchup(self, ids, caps, adam, stream, arr):
         """Adam: the launch that brings the step's rows up to date BEFORE anything reads them (ktup_shard_adam_catchup): the distinct
@@ -358,21 +557,14 @@ class ShardedKtupStepper(_ShardedStepBase):
                  l1=False, target=-1.0, orth=False, ent_pad=-1, group=None, capacity_factor=1.25, use_graphs=True, force_exchange=False,
                  direct=None, overlap_route=True, fused_apply=True, route_beside=False, betas=(0.9, 0.999), opt_step=None, exchange_graph=True,
                  weight_decay=0.0, use_st_gumbel=False, gumbel_seed=0, row_regs=False):
-        self.exchange_graph = bool(exchange_graph)
         # TUP (transUP.py:69-82; run_item_recommendation.py -model_type transup): Et = rel = norm = item2ent = None -- two sharded tables,
         # two small ones.  row_regs: TUP's row regularisers (item_recommendation.py:177-180: normLoss of the batch's user rows, of its
         # [pos ; neg] item rows and of the preference table), added to the stored row gradients by a launch after the step kernel
         self.tup = Et is None
         self.row_regs = bool(row_regs)
-        self.weight_decay = float(weight_decay)
-        self.lazy = is_lazy(kind, weight_decay)
         self.use_st_gumbel = bool(use_st_gumbel)
-        if kind not in KINDS:
-            raise ValueError('row-sparse steps exist for plain SGD, Adagrad and Adam')
-        self.betas = (float(betas[0]), float(betas[1]))
-        self.has_state = kind != 'sgd' or self.lazy
-        self.route_beside = bool(route_beside)
-        if self.lazy and self.route_beside:      # the catch-up needs the route's distinct rows before the step kernel reads them
+        self._init_rule(kind, betas, weight_decay)
+        if self.lazy and route_beside:      # the catch-up needs the route's distinct rows before the step kernel reads them
             raise ValueError('route_beside (the step kernel beside the whole route) does not exist for the lazy rules (Adam, weight decay): '
                              'the catch-up of the rows the route names comes before the step kernel')
         if self.tup and (rel is not None or norm is not None or item2ent is not None):
@@ -380,13 +572,8 @@ class ShardedKtupStepper(_ShardedStepBase):
         self.tables = [Ut, It] if self.tup else [Ut, It, Et]
         self.small = [pref, pref_norm] if self.tup else [pref, pref_norm, rel, norm]
         self.T = T = len(self.tables)
-        self.group = group
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        for t in self.tables:
-            if t.world != self.world or t.rank != self.rank:
-                raise ValueError('the tables must be sharded over the stepper\'s process group')
-        self.kind, self.lr, self.eps, self.max_norm = kind, float(lr), float(eps), float(max_norm)
+        self._init_job(group, force_exchange, capacity_factor)
+        self.lr, self.eps, self.max_norm = float(lr), float(eps), float(max_norm)
         self.l1, self.target, self.orth = bool(l1), float(target), bool(orth)
         self.B = B = int(batch)
         self.d = d = Ut.d
@@ -401,46 +588,27 @@ class ShardedKtupStepper(_ShardedStepBase):
         if not self.tup and (item2ent.dtype != torch.int32 or item2ent.device != dev):
             raise L.KtupError('item2ent must be an int32 device table')
         self.item2ent, self.ent_pad = (None if self.tup else item2ent.contiguous()), int(ent_pad)
-        self.use_graphs = bool(use_graphs)
-        self.overlap_route = bool(overlap_route)
-        # fused_apply: reduce -> norm -> apply as two walks over the per-pair gradients (no W x d gradient buffer in between);
-        # False keeps the three-launch form through Gwire (same results to rounding: the tests run both)
-        self.fused_apply = bool(fused_apply)
-        self._side = torch.cuda.Stream(device=Ut.weight.device) if self.overlap_route else None
-        # force_exchange: take the several-ranks route (five segments, the three all-to-alls and the all-reduce) on ONE rank too --
-        # what a rank of a bigger job runs, minus the wire; with an initialised process group the collectives are real (RCCL at
-        # world 1), without one they are device copies
-        self.multi = self.world > 1 or bool(force_exchange)
-        self.capacity_factor = float(capacity_factor)
         # direct (one rank only): the step kernel gathers straight from the shards by global id -- no pack launch, no compact copy;
         # it needs every item's entity to be a row of Et (no negative map entries; `ent_pad`, if given, is Et's own zero row)
         can_direct = not self.multi and (self.tup or not bool((self.item2ent < 0).any()))
         if direct and not can_direct:
             raise ValueError('direct gathers need a single rank and an item2ent without negative entries')
         self.direct = can_direct if direct is None else bool(direct)
-        W_ = self.world
-        n_dist = [B, 2 * B, 2 * B][:T]                         # entries per table ([u], [pos ; neg], their entities) = at most this many DISTINCT ids
-        if W_ == 1:
-            cap = list(n_dist)
-        else:
-            cap = [min(n, int(math.ceil(self.capacity_factor * n / W_)) + 64) for n in n_dist]
-        self.cap, self.capsum = cap, sum(cap)
-        self.W = W = W_ * self.capsum
+        self._init_capacity([B, 2 * B, 2 * B][:T])             # entries per table: [u], [pos ; neg], their entities
+        W, W_ = self.W, self.world
         self.E = E = (3 if self.tup else 5) * B
         i64 = lambda n, fill=None: torch.empty(n, dtype=torch.int64, device=dev) if fill is None else torch.full((n,), fill, dtype=torch.int64, device=dev)
         i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         lib = L.load()
-        self.u, self.pi, self.ni = i64(B, 0), i64(B, 0), i64(B, 0)
-        self.cursor = torch.zeros(1, dtype=torch.int64, device=dev)       # batch the next step reads (device side, moves by itself)
-        self._feed = (self.u, self.pi, self.ni, 1)
+        self.u, self.pi, self.ni = self._ids = [i64(B, 0), i64(B, 0), i64(B, 0)]
+        self._init_run(use_graphs, overlap_route, exchange_graph, fused_apply, route_beside, opt_step)
         # what a route writes and the step's launches read, TWICE: with batches fed from device columns on one rank, steps alternate between
         # the sets and the route of step s + 1 fills the other set beside the walks of step s (_pipelined); otherwise set 0 is the only one
         # in use.  The attribute names (self.entries, ...) point at the set of the step being bound / run (_use).
         self._sets = [{'entries': i64(E, -1), 'inverse': i64(E, 0), 'send_ids': i64(W, -1), 'pair_map': i32(W + 1),
                        'sort_ws': i32((lib.ktup_shard_route_sort_bytes(E, W) + 3) // 4), 'counters': i32(W_ * T + 1),
                        'acc': torch.zeros(SLOTS + 1, dtype=torch.float64, device=dev)} for _ in range(2)]   # acc: [SLOTS partial sums of squares | the job-wide total]
-        self._par = 0
         self._use(0)
         self.route_ws = torch.empty((lib.ktup_shard_route_workspace_bytes(E) + 7) // 8, dtype=torch.int64, device=dev)
         self.X = f32(W + 1, d)                                # row W stays zero: "no entity" (jTransUP.py:96 padding_idx)
@@ -451,17 +619,12 @@ class ShardedKtupStepper(_ShardedStepBase):
         self.n_loss = 4 if self.row_regs else 2               # [batch-mean BPR terms, orthogonalLoss values (, normLoss of the rows, normLoss(pref))]
         self.loss_sum = f32(self.n_loss)                      # ... summed over the steps that ran
         self.loss_step = f32(self.n_loss)                     # the current step's terms (the apply launch folds and clears them)
-        self.skipped = i32(1)                                 # steps skipped for overflow: never cleared by a launch
         n_g = 4 if (self.orth and not self.tup) else 2
         self.small_g = [f32(P, d) for _ in range(n_g)]        # orth: gP, gPn, gR, gRn; else gA (pref & rel), gC (pref_norm & norm)
         self.small_state = [row_state(s.data, kind, weight_decay) for s in self.small]
         for t in self.tables:
             if not _check_state(t.state, t.weight.data, kind, weight_decay):
                 t.state = row_state(t.weight.data, kind, weight_decay)
-        # Adam: the number of the step being applied, in device memory (the launches are replayed from graphs); shared by the steppers
-        # of a joint schedule.  ktup_shard_step_count moves it just before every apply launch.
-        self.opt_step = opt_step if opt_step is not None else torch.zeros(2, dtype=torch.int64, device=dev)      # [step, two floats of bias corrections]
-        self.steps = 0
         # ST-Gumbel gate (transUP.py:118-170 / jTransUP.py:250-262, -use_st_gumbel): the draws of a step come from a Philox stream whose
         # position lives in device memory (KTUP_GUMBEL_PHILOX_DEV: the step is a replayed graph) and moves by 2 B P per step -- every rank
         # its own stream; set_gumbel_uniforms() feeds recorded uniforms instead (the parity mode of the tests)
@@ -471,41 +634,16 @@ class ShardedKtupStepper(_ShardedStepBase):
             self.gstate = torch.tensor([seed, 0], dtype=torch.int64, device=dev)
             self.gadv = torch.tensor([0, 2 * B * P], dtype=torch.int64, device=dev)
         if self.multi:
-            self.recv_ids = i64(W, -1)
-            self.Xsend = f32(W, d)
-            self.Grecv = f32(W, d)
-            self.cap_own = [max(1, min(W_ * c, t.weight.shape[0])) for c, t in zip(cap, self.tables)]
-            self.W_own = Wo = sum(self.cap_own)
-            self.own_inverse = i64(W, 0)
-            self.own_ids = i64(Wo, -1)
-            self.own_sort = i32((lib.ktup_shard_route_sort_bytes(W, Wo) + 3) // 4)
-            self.own_counters = i32(T + 1)
-            self.own_ws = torch.empty((lib.ktup_shard_route_workspace_bytes(W) + 7) // 8, dtype=torch.int64, device=dev)
-            self.Gown = f32(Wo, d)
-            self.own_xkeys = i32(max(2, lib.ktup_shard_reduce_list_len(W, d)))
-            self.bucket = torch.zeros(n_g * P * d + 2, dtype=torch.float64, device=dev)
-        self._eager = None
-        self._graphs = self._graphs1 = self._cycles = None
-        self._graph_steps = 0
-        self._fed = self._routed = False
+            self._init_exchange(n_g * P * d)
 
-    # ------------------------------------------------------------------------------------------------ launch lists
-    def _bind(self, stream, side=None):
-        """Pre-bound launches (lib.bind) on `stream`, as the segments between the collectives.  One rank with direct gathers: the
-        step kernel needs only the entry list (the route's first launch), so the rest of the route -- hashing, slots, the
-        counting sort: four small latency-bound launches -- is bound to `side` (a second stream) and runs beside it; the
-        segment then reads [init, ('fork', [...]), step, ('join',), ...]."""
+    def _launches(self, stream, side, arr):
+        """The rec step's launches by role, for `_arrange`."""
         B, d, P, W, E, Wn = self.B, self.d, self.P, self.W, self.E, self.world
         Ut, It = self.tables[0], self.tables[1]
         Et = None if self.tup else self.tables[2]
         T = self.T
         pref, pref_norm = self.small[0].data, self.small[1].data
         rel, norm = (None, None) if self.tup else (self.small[2].data, self.small[3].data)
-        keep = self._keep = []                                 # ctypes arrays must outlive the bound launches
-
-        def arr(x):
-            keep.append(x)
-            return ctypes.addressof(x)
         tabs = arr(_ptrs([t.weight.data for t in self.tables]))
         lds = arr(_i64s([t.weight.data.stride(0) for t in self.tables]))
         states = arr(_ptrs([t.state for t in self.tables])) if self.has_state else None
@@ -542,15 +680,11 @@ class ShardedKtupStepper(_ShardedStepBase):
         close = (_p(self.loss_step), self.n_loss, _p(self.loss_sum), _p(self.skipped))
         # one rank, two-walk form: the step kernel adds the stored rows' squared norms itself and the norm walk only corrects for
         # rows that several entries share (dup_only) -- with ids spread over millions of rows it reads almost nothing
-        import os as _os
         # (not with row regularisers: they change the stored rows after the step kernel has summed their squares)
-        dup = (not self.multi) and self.fused_apply and not self.row_regs and _os.environ.get('KTUP_C5_DUP','1') != '0'
+        dup = (not self.multi) and self.fused_apply and not self.row_regs and C5_DUP
         ssq = (_p(self.acc), SLOTS) if dup else (None, 0)
-        # one rank, direct gathers, a second stream: the step kernel reads the id columns itself and runs beside the WHOLE route (its
-        # init launch included); its squared norms go to accumulators of their own that the boundary-norm launch folds in, and that
-        # launch moves the cursor once both branches are done
-        # (measured at config 5: 0.151 ms per step against 0.141 with only the route's last four launches beside the kernel -- the init
-        # launch's 1,024 workgroups delay the step kernel's first tiles -- so it is an option, off by default)
+        # route_beside: the step kernel reads the id columns itself, sums its squared norms into accumulators of its own that the
+        # boundary-norm launch folds in, and that launch moves the cursor (_arrange: the step kernel beside the whole route)
         beside = dup and self.direct and side is not None and self.route_beside
         cols = (None, None, 0)
         fold = (None, 0, None)
@@ -559,9 +693,7 @@ class ShardedKtupStepper(_ShardedStepBase):
             fold = (_p(self.acc_step), SLOTS, _p(self.cursor))
         bind = L.bind
         fu, fp, fn, nb = self._feed
-        def route_phase(phase, on):
-            return self._route_launch(phase, on, keep)
-        route = route_phase(0, stream)
+        parts = {'route': self._route, 'beside': beside}
         gate = (0, None)                                     # KTUP_GUMBEL_OFF / _INPUT (recorded uniforms) / _PHILOX_DEV (device-resident stream position)
         if self.use_st_gumbel:
             gate = (1, _p(self.guni)) if self.guni is not None else (3, _p(self.gstate))
@@ -598,7 +730,10 @@ class ShardedKtupStepper(_ShardedStepBase):
                 gstate.add_(gadv)
         reduce_ = bind('ktup_shard_reduce_rows', _p(self.Gcat), d, d, 3 * B, 2 * B, _p(self.sort_ws), E, W, _p(self.Gwire), d, stream)
         if not self.multi:
-            pack = bind('ktup_shard_pack_wire', T, tabs, lds, cap, d, _p(self.send_ids), 1, _p(X), d, stream)
+            if not self.direct:
+                parts['pack'] = bind('ktup_shard_pack_wire', T, tabs, lds, cap, d, _p(self.send_ids), 1, _p(X), d, stream)
+            if adam:
+                parts['catchup'] = self._catchup(self.send_ids, self.cap, adam, stream, arr)
             nl = [self.Gwire] + norm_list
             nptr, nsz = arr(_ptrs(nl)), arr(_i64s([t.numel() for t in nl]))
             gnorm = bind('ktup_optim_gradnorm_acc', len(nl), nptr, nsz, _p(self.acc), SLOTS, stream)
@@ -619,36 +754,13 @@ class ShardedKtupStepper(_ShardedStepBase):
                 tail = [rnorm] + count + [rapply]
             else:
                 tail = [reduce_, gnorm] + count + [apply_]
-            if self._double():     # this step's route ran beside the previous step's walks (into this buffer set); the next step's runs beside these
-                nxt = [self._route_launch(0, side if side is not None else stream, keep, 1 - self._bind_par)]
-                head = ([self._catchup(self.send_ids, self.cap, adam, stream, arr)] if adam else []) + ([step] if self.direct else [pack, step])
-                # the branch leaves at the step's first launch and is joined in front of its last one: a graph that ENDS in a join pays ~17 us
-                # before the next replay starts (measured), and a route that starts beside the walks ends after them
-                # (joined at the graph's end instead: 0.1217 against 0.1205 ms; the next route on the second stream as a graph of its own with
-                #  events between the replays -- no branch inside the step's graph at all: 0.126; forked after the step kernel, beside the
-                #  walks only: 0.143 -- the branch then ends after the walks and a graph that ends in a late join pays ~17 us)
-                return [[('beside', head + tail[:-1], nxt), ('join',), tail[-1]] if side is not None else head + tail + nxt]
-            if adam:                                         # the whole route, then the catch-up of the rows it named, then whoever reads them
-                catch = self._catchup(self.send_ids, self.cap, adam, stream, arr)
-                return [([route, catch, step] if self.direct else [route, catch, pack, step]) + tail]
-            if beside:
-                return [[('beside', [step], [route_phase(3, side)]), ('join',)] + tail]
-            if self.direct and side is not None:
-                return [[route_phase(1, stream), ('beside', [step], [route_phase(2, side)]), ('join',)] + tail]
-            return [([route, step] if self.direct else [route, pack, step]) + tail]
-        # ---- several ranks (or one in exchange form): five segments around the three all-to-alls and the all-reduce.  What does not lie on
-        # the path of the data rides on the second stream: the counting sort of the entries (only the gradient reduction reads it) and the
-        # zero-fill of the few wire rows that several entries share run beside the pack launch, the owner's route of the requested rows
-        # (only the owner's reduction reads it) beside the step kernel.  The requester's reduction STORES its rows (ktup_shard_reduce_store):
-        # no zero-filled 42 MB buffer, no read-modify-write.
-        on = side if side is not None else stream
-
-        def par(main, beside):
-            return [('beside', main, beside), ('join',)] if side is not None else beside + main
+            parts.update(step=[step], tail=tail)
+            return parts
+        on = side if side is not None else stream                # the second stream, where there is one
         capo = arr(_i64s(self.cap_own))
         eoff_o = arr(_i64s([0, self.cap[0], self.cap[0] + self.cap[1], self.capsum][:T] + [self.capsum]))
         pack = bind('ktup_shard_pack_wire', T, tabs, lds, cap, d, _p(self.recv_ids), Wn, _p(self.Xsend), d, stream)
-        sort_ = route_phase(5, on)
+        sort_ = self._route(5, on)
         zshared = bind('ktup_shard_zero_shared_rows', _p(self.sort_ws), E, W, _p(inv), _p(self.Gwire), d, d, on)
         rep_p, rep_n = self._small_ws()
         rstore = bind('ktup_shard_reduce_store_fold', _p(self.Gcat), d, d, 3 * B, 2 * B, _p(self.sort_ws), E, W, _p(self.Gwire), d,
@@ -678,37 +790,17 @@ class ShardedKtupStepper(_ShardedStepBase):
             own_tail = [[onorm, pack_b], [fin_b] + count + [oapply]]
         else:
             own_tail = [[oreduce, gnorm, pack_b], [fin_b] + count + [apply_]]
-        whole = side is not None and self._whole_step_graph() and self._open_branch()      # one graph: a branch may stay open across the exchanges
-        head, nxt = [route_phase(4, stream)], []
-        if self._pipelined():           # this step's route ran during the previous step (into this buffer set)
-            head = []
-            nxt = [self._route_launch(4, on, keep, 1 - self._bind_par)]
-
-        def later(first):
-            """Whole-step graph: the NEXT step's route leaves the main stream at the requester's reduction and is joined after the bucket
-            launch (55 us of main-stream work -- reduction, gradient exchange, norm walk, bucket -- against ~30 of route).  On the branch
-            that carries the sort and the owner's route it ended 23 us after the step kernel and the reduction waited for it
-            (profiles/r06_config5_timeline.txt, first collection)."""
-            if not nxt:
-                return [first]
-            own_tail[0] = own_tail[0] + [('join',)]
-            return [('beside', [first], nxt)]
-        if adam:    # the owner's route of the requested rows moves in front of the pack launch: the catch-up needs its DISTINCT rows
-            catch = self._catchup(self.own_ids, self.cap_own, adam, stream, arr)
-            if whole:
-                return [head, [oroute_on(stream), catch, ('beside', [pack], [sort_, zshared])], [step, ('join',)] + later(rstore)] + own_tail
-            return [head, [oroute_on(stream), catch] + par([pack], [sort_, zshared]), par([step, rstore], nxt) if nxt else [step, rstore]] + own_tail
-        if whole:   # sort, zero-fill, the owner's route (and the next step's route): one branch from the id exchange to the end of the step kernel
-            return [head, [('beside', [pack], [sort_, zshared, oroute_on(on)])], [step, ('join',)] + later(rstore)] + own_tail
-        return [head, par([pack], [sort_, zshared]), par([step, rstore], [oroute_on(on)] + nxt)] + own_tail
+        if adam:
+            parts['catchup'] = self._catchup(self.own_ids, self.cap_own, adam, stream, arr)
+        parts.update(step=[step], pack=pack, sort_=sort_, zshared=zshared, rstore=rstore, oroute=oroute_on, own_tail=own_tail)
+        return parts
 
     def _small_ws(self):
         """(pointer, bytes) of the step kernel's REPLICAS of the preference tables' gradients (ktup_train_rec_step_rows_ws: tile workgroup b
         adds its partial sums to replica b mod 8 instead of all 256 workgroups to one copy), or (None, 0): the launch that follows the step
         kernel folds them into gP / gPn (/ gR / gRn) -- the norm walk on one rank, the requester's reduction on several -- so the forms
         without such a launch (one rank through a gradient buffer) keep the plain flush.  KTUP_STEP_SMALL_WS=0: none."""
-        import os
-        if os.environ.get('KTUP_STEP_SMALL_WS', '1') == '0' or (not self.multi and not self.fused_apply):
+        if not STEP_SMALL_WS or (not self.multi and not self.fused_apply):
             return None, 0
         if getattr(self, '_small_ws_buf', None) is None:
             n = int(L.load().ktup_train_rec_step_rows_ws_bytes(self.B, self.P, self.d))
@@ -747,40 +839,6 @@ class ShardedKtupStepper(_ShardedStepBase):
                       _p(S['entries']), self.world, ctypes.addressof(cap), _p(S['inverse']), _p(S['send_ids']), _p(S['pair_map']), _p(S['sort_ws']),
                       _p(S['counters']), _p(S['acc']), SLOTS if self.multi else SLOTS + 1, _p(self.route_ws), phase, on)
 
-    def _bind_route(self, stream):
-        keep = []
-        return self._route_launch(0 if not self.multi else 4, stream, keep), keep
-
-    # ------------------------------------------------------------------------------------------------ the step
-    def load_batch(self, u, pos_items, neg_items):
-        """Copy a batch into the step's static id buffers (skip it by writing step.u / step.pi / step.ni in place, or by set_feed)."""
-        if self._feed[0] is not self.u:
-            self.set_feed(None)
-        self.u.copy_(u, non_blocking=True); self.pi.copy_(pos_items, non_blocking=True); self.ni.copy_(neg_items, non_blocking=True)
-
-    def set_feed(self, columns):
-        """Device-fed batches: columns = (u, pos_items, neg_items), contiguous int64 device tensors of n_batches x B ids each (an epoch
-        of pre-drawn batches, or whatever a device-side sampler refills in place).  Step s reads batch (cursor mod n_batches) and the
-        step's own first launches move the device cursor on: `run()` then needs no per-step copy or argument.  None: back to the
-        static one-batch buffers that load_batch fills."""
-        if columns is None:
-            self._feed = (self.u, self.pi, self.ni, 1)
-        else:
-            u, p, n = columns
-            for c in (u, p, n):
-                if c.dtype != torch.int64 or c.device != self.dev or not c.is_contiguous() or c.numel() % self.B or c.numel() != u.numel():
-                    raise L.KtupError('feed columns are contiguous int64 device tensors of n_batches x B ids each')
-            self._feed = (u, p, n, u.numel() // self.B)
-        self._fed, self._routed, self._par = columns is not None, False, 0
-        self.cursor.zero_()
-        self._eager = None
-        self._graphs = self._graphs1 = self._cycles = None                   # the column addresses are baked into the bound launches
-
-    def __call__(self, u=None, pos_items=None, neg_items=None):
-        if u is not None:
-            self.load_batch(u, pos_items, neg_items)
-        self.run()
-
 
 class ShardedKgStepper(_ShardedStepBase):
     """KTUP's kg step (knowledgable_recommendation.py:345-383, 394-403) on the row-sharded entity table:
@@ -800,23 +858,12 @@ class ShardedKgStepper(_ShardedStepBase):
     def __init__(self, Et, rel, norm, batch, kind='adagrad', lr=0.005, eps=1e-10, max_norm=0.0, l1=False, margin=1.0, kg_lambda=1.0,
                  transh=True, regs=7, small_state=None, group=None, capacity_factor=1.25, use_graphs=True, force_exchange=False,
                  direct=None, overlap_route=True, betas=(0.9, 0.999), opt_step=None, exchange_graph=True, weight_decay=0.0):
-        self.exchange_graph = bool(exchange_graph)
-        self.weight_decay = float(weight_decay)
-        self.lazy = is_lazy(kind, weight_decay)
-        if kind not in KINDS:
-            raise ValueError('row-sparse steps exist for plain SGD, Adagrad and Adam')
-        self.betas = (float(betas[0]), float(betas[1]))
-        self.has_state = kind != 'sgd' or self.lazy
-
+        self._init_rule(kind, betas, weight_decay)
         self.tables = [Et]
         self.transh = bool(transh)
         self.small = [rel, norm] if self.transh else [rel]
-        self.group = group
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        if Et.world != self.world or Et.rank != self.rank:
-            raise ValueError('the entity table must be sharded over the stepper\'s process group')
-        self.kind, self.lr, self.eps, self.max_norm = kind, float(lr), float(eps), float(max_norm)
+        self._init_job(group, force_exchange, capacity_factor)
+        self.lr, self.eps, self.max_norm = float(lr), float(eps), float(max_norm)
         self.l1, self.margin, self.kg_lambda, self.regs = bool(l1), float(margin), float(kg_lambda), int(regs)
         self.B = B = int(batch)
         self.d = d = Et.d
@@ -829,32 +876,21 @@ class ShardedKgStepper(_ShardedStepBase):
         lib = L.load()
         if not lib.ktup_train_step_supported(1 if self.transh else 2, d, P):
             raise L.KtupError('no fused kg step kernel for d=%d (ktup_train_step_supported)' % d)
-        self.use_graphs = bool(use_graphs)
-        self.overlap_route = bool(overlap_route)
-        self._side = torch.cuda.Stream(device=dev) if self.overlap_route else None
-        self.multi = self.world > 1 or bool(force_exchange)
-        self.capacity_factor = float(capacity_factor)
-        can_direct = not self.multi
-        if direct and not can_direct:
+        if direct and self.multi:
             raise ValueError('direct gathers need a single rank')
-        self.direct = can_direct if direct is None else bool(direct)
-        W_ = self.world
-        n_dist = 4 * B
-        cap = [n_dist if W_ == 1 else min(n_dist, int(math.ceil(self.capacity_factor * n_dist / W_)) + 64)]
-        self.cap, self.capsum = cap, cap[0]
-        self.W = W = W_ * self.capsum
+        self.direct = (not self.multi) if direct is None else bool(direct)
+        self._init_capacity([4 * B])                                     # entries: [ph ; pt ; nh ; nt]
+        W, W_ = self.W, self.world
         self.E = E = 4 * B
         i64 = lambda n, fill=None: torch.empty(n, dtype=torch.int64, device=dev) if fill is None else torch.full((n,), fill, dtype=torch.int64, device=dev)
         i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-        self.cols = [i64(B, 0) for _ in range(6)]                        # ph, pt, pr, nh, nt, nr
-        self.cursor = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._feed = tuple(self.cols) + (1,)
+        self.cols = self._ids = [i64(B, 0) for _ in range(6)]            # ph, pt, pr, nh, nt, nr
+        self._init_run(use_graphs, overlap_route, exchange_graph, opt_step=opt_step)
         # the route's output twice (ShardedKtupStepper.__init__: steps fed from device columns alternate between the sets)
         self._sets = [{'entries': i64(E, 0), 'rels': i64(2 * B, 0), 'inverse': i64(E, 0), 'send_ids': i64(W, -1),
                        'sort_ws': i32((lib.ktup_shard_route_sort_bytes(E, W) + 3) // 4), 'counters': i32(W_ + 1),
                        'acc': torch.zeros(SLOTS + 1, dtype=torch.float64, device=dev)} for _ in range(2)]
-        self._par = 0
         self._use(0)
         self.order = i32(B)
         self.route_ws = torch.empty((lib.ktup_shard_route_workspace_bytes(E) + 7) // 8, dtype=torch.int64, device=dev)
@@ -863,7 +899,6 @@ class ShardedKgStepper(_ShardedStepBase):
         self.Gwire = f32(W, d)
         self.xkeys = i32(max(2, lib.ktup_shard_reduce_list_len(E, d)))
         self.loss_sum, self.loss_step = f32(4), f32(4)
-        self.skipped = i32(1)
         self.small_g = [f32(P, d) for _ in self.small]
         if self.has_state:
             self.small_state = list(small_state) if small_state is not None else [row_state(s.data, kind, weight_decay) for s in self.small]
@@ -871,34 +906,13 @@ class ShardedKgStepper(_ShardedStepBase):
                 Et.state = row_state(Et.weight.data, kind, weight_decay)
         else:
             self.small_state = [None] * len(self.small)
-        self.opt_step = opt_step if opt_step is not None else torch.zeros(2, dtype=torch.int64, device=dev)      # [step, two floats of bias corrections]
-        self.steps = 0
         if self.multi:
-            self.recv_ids = i64(W, -1)
-            self.Xsend = f32(W, d)
-            self.Grecv = f32(W, d)
-            self.cap_own = [max(1, min(W_ * cap[0], Et.weight.shape[0]))]
-            self.W_own = Wo = self.cap_own[0]
-            self.own_inverse = i64(W, 0)
-            self.own_ids = i64(Wo, -1)
-            self.own_sort = i32((lib.ktup_shard_route_sort_bytes(W, Wo) + 3) // 4)
-            self.own_counters = i32(1 + 1)
-            self.own_ws = torch.empty((lib.ktup_shard_route_workspace_bytes(W) + 7) // 8, dtype=torch.int64, device=dev)
-            self.Gown = f32(Wo, d)
-            self.own_xkeys = i32(max(2, lib.ktup_shard_reduce_list_len(W, d)))
-            self.bucket = torch.zeros(len(self.small) * P * d + 2, dtype=torch.float64, device=dev)
-        self._eager = None
-        self._graphs = self._graphs1 = self._cycles = None
-        self._fed = self._routed = False
+            self._init_exchange(len(self.small) * P * d)
 
-    def _bind(self, stream, side=None):
+    def _launches(self, stream, side, arr):
+        """The kg step's launches by role, for `_arrange`."""
         B, d, P, W, E, Wn = self.B, self.d, self.P, self.W, self.E, self.world
         Et = self.tables[0]
-        keep = self._keep = []
-
-        def arr(x):
-            keep.append(x)
-            return ctypes.addressof(x)
         tabs = arr(_ptrs([Et.weight.data]))
         lds = arr(_i64s([Et.weight.data.stride(0)]))
         states = arr(_ptrs([Et.state])) if self.has_state else None
@@ -916,10 +930,7 @@ class ShardedKgStepper(_ShardedStepBase):
         close = (_p(self.loss_step), 4, _p(self.loss_sum), _p(self.skipped))
         skip_i = self.counters.data_ptr() + 4 * Wn
         bind = L.bind
-        f = self._feed
-
-        def route_phase(phase, on):
-            return self._route_launch(phase, on, keep)
+        parts = {'route': self._route}
         order = bind('ktup_shard_kg_rel_order', _p(self.rels), B, P, _p(self.order), stream)
         if self.direct:
             Esrc, lde, ent_ids, ent_pad = Et.weight.data, Et.weight.data.stride(0), self.entries, -1
@@ -929,34 +940,23 @@ class ShardedKgStepper(_ShardedStepBase):
                     _p(self.order), B, int(self.l1), self.margin, self.kg_lambda, self.regs, _p(self.loss_step), _p(self.GE), _p(gR), _p(gN),
                     *((None, 0) if self.multi else (_p(self.acc), SLOTS)), stream)
         if not self.multi:
-            pack = bind('ktup_shard_pack_wire', 1, tabs, lds, cap, d, _p(self.send_ids), 1, _p(self.X), d, stream)
+            if not self.direct:
+                parts['pack'] = bind('ktup_shard_pack_wire', 1, tabs, lds, cap, d, _p(self.send_ids), 1, _p(self.X), d, stream)
+            if adam:
+                parts['catchup'] = self._catchup(self.send_ids, self.cap, adam, stream, arr)
             rnorm = bind('ktup_shard_reduce_norm', _p(self.GE), d, d, E, 0, _p(self.sort_ws), E, W, _p(self.Gwire), d, _p(self.xkeys), n_small,
                          sgp, P * d, 1.0, _p(self.acc), SLOTS, 1, None, 0, None, stream)
             rapply = bind('ktup_shard_reduce_apply', kind, 1, tabs, lds, states, slds, cap, _p(self.send_ids), 1, _p(self.GE), d, d, E, 0,
                           _p(self.sort_ws), E, _p(self.Gwire), d, _p(self.xkeys), n_small, P, sgp, sp0p, ss0p, None, None, None, self.lr,
                           self.eps, _p(self.acc), SLOTS, self.max_norm, skip_i, None, *close, adam, stream)
             count = [bind('ktup_shard_step_count', _p(self.opt_step), skip_i, None, self.betas[0], self.betas[1], stream)] if adam else []
-            if self._double():     # routed beside the previous step's walks; the next step's route (the other buffer set) beside these
-                nxt = [self._route_launch(0, side if side is not None else stream, keep, 1 - self._bind_par)]
-                head = ([self._catchup(self.send_ids, self.cap, adam, stream, arr)] if adam else []) + ([] if self.direct else [pack]) + [order, step]
-                walks = [rnorm] + count + [rapply]
-                return [[('beside', head + walks[:-1], nxt), ('join',), walks[-1]] if side is not None else head + walks + nxt]
-            if adam:
-                catch = self._catchup(self.send_ids, self.cap, adam, stream, arr)
-                return [[route_phase(0, stream), catch] + ([] if self.direct else [pack]) + [order, step, rnorm] + count + [rapply]]
-            if self.direct and side is not None:
-                return [[route_phase(1, stream), ('beside', [order, step], [route_phase(2, side)]), ('join',), rnorm] + count + [rapply]]
-            return [[route_phase(0, stream)] + ([] if self.direct else [pack]) + [order, step, rnorm] + count + [rapply]]
-        # several ranks: as ShardedKtupStepper._bind -- the sort and the shared rows' zero-fill beside the pack launch, the owner's route
-        # beside the step kernel, the requester's reduction storing its rows
-        on = side if side is not None else stream
-
-        def par(main, beside):
-            return [('beside', main, beside), ('join',)] if side is not None else beside + main
+            parts.update(step=[order, step], tail=[rnorm] + count + [rapply])
+            return parts
+        on = side if side is not None else stream                # the second stream, where there is one
         capo = arr(_i64s(self.cap_own))
         eoff_o = arr(_i64s([0, self.capsum]))
         pack = bind('ktup_shard_pack_wire', 1, tabs, lds, cap, d, _p(self.recv_ids), Wn, _p(self.Xsend), d, stream)
-        sort_ = route_phase(5, on)
+        sort_ = self._route(5, on)
         zshared = bind('ktup_shard_zero_shared_rows', _p(self.sort_ws), E, W, _p(self.inverse), _p(self.Gwire), d, d, on)
         rstore = bind('ktup_shard_reduce_store', _p(self.GE), d, d, E, 0, _p(self.sort_ws), E, W, _p(self.Gwire), d, stream)
 
@@ -974,25 +974,10 @@ class ShardedKgStepper(_ShardedStepBase):
                       *close, adam, stream)
         count = [bind('ktup_shard_step_count', _p(self.opt_step), None, self.bucket.data_ptr() + 8 * (N + 1), self.betas[0], self.betas[1], stream)] if adam else []
         own_tail = [[onorm, pack_b], [fin_b] + count + [oapply]]
-        whole = side is not None and self._whole_step_graph() and self._open_branch()
-        head, nxt = [route_phase(4, stream)], []
-        if self._pipelined():
-            head = []
-            nxt = [self._route_launch(4, on, keep, 1 - self._bind_par)]
-
-        def later(first):           # (ShardedKtupStepper._bind: the next step's route from the requester's reduction to the bucket launch)
-            if not nxt:
-                return [first]
-            own_tail[0] = own_tail[0] + [('join',)]
-            return [('beside', [first], nxt)]
         if adam:
-            catch = self._catchup(self.own_ids, self.cap_own, adam, stream, arr)
-            if whole:
-                return [head, [oroute_on(stream), catch, ('beside', [pack], [sort_, zshared])], [order, step, ('join',)] + later(rstore)] + own_tail
-            return [head, [oroute_on(stream), catch] + par([pack], [sort_, zshared]), par([order, step, rstore], nxt) if nxt else [order, step, rstore]] + own_tail
-        if whole:
-            return [head, [('beside', [pack], [sort_, zshared, oroute_on(on)])], [order, step, ('join',)] + later(rstore)] + own_tail
-        return [head, par([pack], [sort_, zshared]), par([order, step, rstore], [oroute_on(on)] + nxt)] + own_tail
+            parts['catchup'] = self._catchup(self.own_ids, self.cap_own, adam, stream, arr)
+        parts.update(step=[order, step], pack=pack, sort_=sort_, zshared=zshared, rstore=rstore, oroute=oroute_on, own_tail=own_tail)
+        return parts
 
     def _route_launch(self, phase, on, keep, par=None):
         S = self._sets[self._bind_par if par is None else par]
@@ -1002,37 +987,6 @@ class ShardedKgStepper(_ShardedStepBase):
         return L.bind('ktup_shard_route_kg', _p(f[0]), _p(f[1]), _p(f[2]), _p(f[3]), _p(f[4]), _p(f[5]), self.B, f[6], _p(self.cursor),
                       _p(S['entries']), _p(S['rels']), self.world, ctypes.addressof(cap), _p(S['inverse']), _p(S['send_ids']), _p(S['sort_ws']),
                       _p(S['counters']), _p(S['acc']), SLOTS if self.multi else SLOTS + 1, _p(self.route_ws), phase, on)
-
-    def _bind_route(self, stream):
-        keep = []
-        return self._route_launch(0 if not self.multi else 4, stream, keep), keep
-
-    def load_batch(self, ph, pt, pr, nh, nt, nr):
-        if self._feed[0] is not self.cols[0]:
-            self.set_feed(None)
-        for dst, src in zip(self.cols, (ph, pt, pr, nh, nt, nr)):
-            dst.copy_(src, non_blocking=True)
-
-    def set_feed(self, columns):
-        """columns = (ph, pt, pr, nh, nt, nr): contiguous int64 device tensors of n_batches x B ids each; step s reads batch
-        (cursor mod n_batches) and moves the device cursor on.  None: back to the static buffers load_batch fills."""
-        if columns is None:
-            self._feed = tuple(self.cols) + (1,)
-        else:
-            cs = tuple(columns)
-            for c in cs:
-                if c.dtype != torch.int64 or c.device != self.dev or not c.is_contiguous() or c.numel() % self.B or c.numel() != cs[0].numel():
-                    raise L.KtupError('feed columns are contiguous int64 device tensors of n_batches x B ids each')
-            self._feed = cs + (cs[0].numel() // self.B,)
-        self._fed, self._routed, self._par = columns is not None, False, 0
-        self.cursor.zero_()
-        self._eager = None
-        self._graphs = self._graphs1 = self._cycles = None
-
-    def __call__(self, *ids):
-        if ids:
-            self.load_batch(*ids)
-        self.run()
 
 
 class ShardedKtupJoint(object):
