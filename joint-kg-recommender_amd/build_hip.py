@@ -19,16 +19,31 @@ HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-Wall', '-Wno-unused-function']
 # SLP packs scalar-operand FMAs into v_pk_fma_f32, which needs SGPR operands in aligned pairs (one s_mov per FMA): off
 # for the kernels that feed FMAs from SGPRs.
-PER_FILE_FLAGS = {'ktup_score_pref.hip': ['-fno-slp-vectorize'], 'ktup_eval.hip': ['-fno-slp-vectorize']}
+PER_FILE_FLAGS = {'ktup_score_pref.hip': ['-fno-slp-vectorize'], 'ktup_eval.hip': ['-fno-slp-vectorize'],
+                  'ktup_transd_eval.hip': ['-fno-slp-vectorize']}
+# Extension directories under csrc/, each with its own C header under include/: compiled into the same library (objects are
+# prefixed with the directory's name).  csrc/*.hip itself stays the set of translation units the committed profiles were taken from.
+EXTENSIONS = {'transd': 'ktup_transd.h'}
 
 
 def _sources():
-    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
+    srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
+    for ext in sorted(EXTENSIONS):
+        srcs += sorted(os.path.join(CSRC, ext, f) for f in os.listdir(os.path.join(CSRC, ext)) if f.endswith('.hip'))
+    return srcs
 
 
 def _headers():
-    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + \
-        [os.path.join(os.path.dirname(HERE), 'include', 'ktup_hip.h')]
+    inc = os.path.join(os.path.dirname(HERE), 'include')
+    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + [os.path.join(inc, 'ktup_hip.h')]
+    for ext, header in sorted(EXTENSIONS.items()):
+        hdrs += [os.path.join(CSRC, ext, f) for f in os.listdir(os.path.join(CSRC, ext)) if f.endswith('.h')] + [os.path.join(inc, header)]
+    return hdrs
+
+
+def _obj(src):
+    sub = os.path.relpath(os.path.dirname(src), CSRC)
+    return os.path.join(OBJ, ('' if sub == '.' else sub.replace(os.sep, '_') + '_') + os.path.basename(src)[:-4] + '.o')
 
 
 def _stale(target, deps):
@@ -39,7 +54,7 @@ def _stale(target, deps):
 
 
 def _compile(src, extra):
-    obj = os.path.join(OBJ, os.path.basename(src)[:-4] + '.o')
+    obj = _obj(src)
     cmd = [HIPCC] + FLAGS + PER_FILE_FLAGS.get(os.path.basename(src), []) + extra + ['-c', src, '-o', obj]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=OBJ)
     return src, obj, r.returncode, r.stdout + r.stderr
@@ -49,8 +64,8 @@ def build(force=False, save_temps=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     srcs, hdrs = _sources(), _headers()
     extra = ['-save-temps'] if save_temps else []
-    todo = [s for s in srcs if force or _stale(os.path.join(OBJ, os.path.basename(s)[:-4] + '.o'), [s] + hdrs)]
-    objs = [os.path.join(OBJ, os.path.basename(s)[:-4] + '.o') for s in srcs]
+    todo = [s for s in srcs if force or _stale(_obj(s), [s] + hdrs)]
+    objs = [_obj(s) for s in srcs]
     if todo:
         with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(todo))) as ex:
             for src, obj, rc, out in ex.map(lambda s: _compile(s, extra), todo):

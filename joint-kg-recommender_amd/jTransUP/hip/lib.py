@@ -162,6 +162,19 @@ _RESTYPE = {'ktup_last_error': ctypes.c_char_p, 'ktup_shard_reduce_list_len': ct
             'ktup_score_kg_bwd_workspace_bytes': ctypes.c_size_t, 'ktup_score_bprmf_bwd_workspace_bytes': ctypes.c_size_t,
             'ktup_train_rec_step_rows_ws_bytes': ctypes.c_size_t}
 
+# The TransD extension of the ABI (include/ktup_transd.h; kernels under csrc/transd/, same library).  A table of its own: SIGNATURES
+# mirrors ktup_hip.h symbol for symbol; the two are to be merged together with the two headers.
+SIGNATURES_TRANSD = {
+    'ktup_score_transd_fwd': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_p, c_p],
+    'ktup_score_transd_bwd': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    'ktup_eval_transd_workspace_bytes': [c_i, c_l],
+    'ktup_eval_transd_scores': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_l, c_i, c_i, c_p, c_l, c_p, c_p],
+    'ktup_eval_kg_ranks_transd_workspace_bytes': [c_i, c_l, c_l],
+    'ktup_eval_kg_ranks_transd': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
+                                  c_p, c_l, c_p, c_p],
+}
+_RESTYPE.update({'ktup_eval_transd_workspace_bytes': ctypes.c_size_t, 'ktup_eval_kg_ranks_transd_workspace_bytes': ctypes.c_size_t})
+
 _lib = None
 
 
@@ -181,7 +194,7 @@ def load():
         raise KtupError('libktup_hip.so not found at %s -- build it with '
                         '`python joint-kg-recommender_amd/build_hip.py` (there is no CPU fallback)' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_TRANSD.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, ctypes.c_int)

@@ -217,6 +217,44 @@ class _ScoreTransR(Function):
         return gE, gR, gM, None, None, None, None
 
 
+def _pitched_zeros(t):
+    """A zero-filled gradient buffer with the row pitch of table `t` (the kernels address a gradient buffer like its table)."""
+    return torch.zeros(t.shape[0], t.stride(0), dtype=torch.float32, device=t.device)[:, :t.shape[1]]
+
+
+class _ScoreTransD(Function):
+    @staticmethod
+    def forward(ctx, E, R, Ep, Rp, h, t, r, l1):
+        dev = _dev(_table('entity table', E)); _table('relation table', R)
+        _table('entity projection table', Ep); _table('relation projection table', Rp)
+        if Ep.shape != E.shape or Rp.shape != R.shape or R.shape[1] != E.shape[1]:
+            raise L.KtupError('TransD tables must be (n_ent, d), (n_rel, d) and their projection tables of the same shapes')
+        n = h.numel(); h = _ids('h', h, dev); t = _ids('t', t, dev, n); r = _ids('r', r, dev, n)
+        score = torch.empty(n, dtype=torch.float32, device=dev)
+        L.call('ktup_score_transd_fwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(Ep), Ep.stride(0), _p(Rp), Rp.stride(0), E.shape[1],
+               _p(h), _p(t), _p(r), n, int(l1), _p(score), _stream(dev))
+        ctx.save_for_backward(E, R, Ep, Rp, h, t, r); ctx.l1 = int(l1)
+        return score
+
+    @staticmethod
+    def backward(ctx, gs):
+        E, R, Ep, Rp, h, t, r = ctx.saved_tensors
+        gs = _vec(gs, h.numel())
+        tabs = (E, R, Ep, Rp)
+        bufs, rets = _grad_targets(*tabs)
+        for k, tab in enumerate(tabs):       # a fresh buffer of a table with padded rows: the table's pitch, not a dense one
+            if rets[k] is not None and tab.stride(0) != tab.shape[1]:
+                bufs[k] = rets[k] = _pitched_zeros(tab)
+        L.call('ktup_score_transd_bwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(Ep), Ep.stride(0), _p(Rp), Rp.stride(0), E.shape[1],
+               _p(h), _p(t), _p(r), h.numel(), ctx.l1, _p(gs), _p(bufs[0]), _p(bufs[1]), _p(bufs[2]), _p(bufs[3]), _stream(E.device))
+        return rets[0], rets[1], rets[2], rets[3], None, None, None, None
+
+
+def score_transd(E, R, Ep, Rp, h, t, r, l1):
+    """transD.py:61-76: dist(h_perp + r - t_perp), e_perp = e + (e . e_p) r_p."""
+    return _ScoreTransD.apply(E, R, Ep, Rp, h, t, r, l1)
+
+
 def score_transe(E, R, h, t, r, l1):
     """transE.py:51-63."""
     return _ScoreTransE.apply(E, R, h, t, r, l1)
@@ -495,6 +533,44 @@ def eval_transh(E, R, N, q, r, l1, head, candidates=None):
     L.call('ktup_eval_transh_scores', _p(E), E.stride(0), _p(R), R.stride(0), _p(N), N.stride(0), E.shape[1], _p(C), C.stride(0),
            C.shape[0], _p(q), _p(r), nq, int(l1), int(head), _p(out), out.stride(0), _p(ws), _stream(dev))
     return out
+
+
+@torch.no_grad()
+def eval_transd(E, R, Ep, Rp, q, r, l1, head, candidates=None):
+    """transD.py:78-134 -> (len(q), n_candidates): dist(c - e - (e . a) b) with a = the QUERY entity's projection row, b = the
+    relation's (ktup_eval_transd_scores; squared L2 on the matrix cores at its widths, the pair kernel otherwise)."""
+    dev = _dev(_table('entity table', E)); _table('relation table', R)
+    _table('entity projection table', Ep); _table('relation projection table', Rp)
+    C = E if candidates is None else _table('candidate table', candidates)
+    nq = q.numel(); q = _ids('q', q, dev); r = _ids('r', r, dev, nq)
+    out = torch.empty(nq, C.shape[0], dtype=torch.float32, device=dev)
+    ws = _scratch(L.load().ktup_eval_transd_workspace_bytes(E.shape[1], nq), dev)
+    L.call('ktup_eval_transd_scores', _p(E), E.stride(0), _p(Ep), Ep.stride(0), _p(R), R.stride(0), _p(Rp), Rp.stride(0), E.shape[1],
+           _p(C), C.stride(0), C.shape[0], _p(q), _p(r), nq, int(l1), int(head), _p(out), out.stride(0), _p(ws), _stream(dev))
+    return out
+
+
+@torch.no_grad()
+def eval_kg_ranks_transd(E, R, Ep, Rp, q, r, l1, head, descending, gold_off, gold_ids, filt_off=None, filt_ids=None, candidates=None,
+                         chunk=512):
+    """eval_kg_ranks for TransD (ktup_eval_kg_ranks_transd): the score matrix of `chunk` keys at a time + K18, the loop under the C ABI.
+    -> int32 [gold_off[-1]]; -1 = a gold id that is itself filtered."""
+    nq = q.numel()
+    if filt_ids is not None and filt_ids.numel() == 0:
+        filt_off = filt_ids = None
+    if gold_off.numel() != nq + 1 or (filt_off is not None and filt_off.numel() != nq + 1):      # (a shape check: before anything else)
+        raise L.KtupError('eval_kg_ranks_transd: CSR offsets need len(q) + 1 entries')
+    dev = _dev(_table('entity table', E)); _table('relation table', R)
+    _table('entity projection table', Ep); _table('relation projection table', Rp)
+    C = E if candidates is None else _table('candidate table', candidates)
+    q = _ids('q', q, dev); r = _ids('r', r, dev, nq)
+    ranks = torch.empty(max(gold_ids.numel(), 1), dtype=torch.int32, device=dev)
+    chunk = max(1, min(int(chunk), max(nq, 1)))
+    ws = _scratch(L.load().ktup_eval_kg_ranks_transd_workspace_bytes(E.shape[1], C.shape[0], chunk), dev)
+    L.call('ktup_eval_kg_ranks_transd', _p(E), E.stride(0), _p(Ep), Ep.stride(0), _p(R), R.stride(0), _p(Rp), Rp.stride(0), E.shape[1],
+           _p(C), C.stride(0), C.shape[0], _p(q), _p(r), nq, int(l1), int(head), int(bool(descending)), _p(filt_off), _p(filt_ids),
+           _p(gold_off), _p(gold_ids), _p(ranks), chunk, _p(ws), _stream(dev))
+    return ranks
 
 
 KG_TRANSE, KG_TRANSH = 0, 1

@@ -1,7 +1,7 @@
 """Candidate-shard scoring for evaluation with the catalogue split over the ranks (`-shard_eval_candidates`).
 
 The reference's evaluate* methods score every query against the WHOLE catalogue (bprmf.py:51-54, transUP.py:84-102,
-jTransUP.py:163-247, transE.py:65-105, transH.py:73-121).  Here a rank scores its contiguous candidate slice [lo, hi) only --
+jTransUP.py:163-247, transE.py:65-105, transH.py:73-121, transD.py:78-134).  Here a rank scores its contiguous candidate slice [lo, hi) only --
 the same kernels on a row slice of the candidate table -- and the ranking is completed across ranks by
 parallel.sharded_topk / parallel.sharded_gold_ranks.  Returns None for models without a sliceable candidate table (TransR
 projects candidates per relation; shared-embedding KTUP re-maps ids): the drivers then deal whole batches to the ranks."""
@@ -43,4 +43,7 @@ def kg_shard_fn(model, head):
     if name == 'TransHModel' or (name == 'jTransUPModel' and not model.is_share):
         E, R, N = model.ent_embeddings.weight, model.rel_embeddings.weight, model.norm_embeddings.weight
         return E.shape[0], lambda q, r, lo, hi: ops.eval_transh(E, R, N, q, r, model.L1_flag, head, candidates=E[lo:hi])
+    if name == 'TransDModel':
+        E, R, Ep, Rp = model._tables()
+        return E.shape[0], lambda q, r, lo, hi: ops.eval_transd(E, R, Ep, Rp, q, r, model.L1_flag, head, candidates=E[lo:hi])
     return None

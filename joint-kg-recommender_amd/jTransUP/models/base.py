@@ -12,14 +12,14 @@ from jTransUP.utils import flags as gflags
 
 # -model_type -> module under jTransUP.models that provides build_model(...)
 ACCELERATED = {'transup': 'transUP', 'bprmf': 'bprmf', 'transe': 'transE', 'transh': 'transH', 'transr': 'transR',
-               'jtransup': 'jTransUP', 'cke': 'CKE', 'cfkg': 'CFKG', 'fm': 'fm', 'cofm': 'cofm'}
-REFERENCE_ONLY = ('transd',)      # TransD: outside SURVEY.md section 8 (and its evaluateTail has a NameError in the reference, transD.py:127)
+               'transd': 'transD', 'jtransup': 'jTransUP', 'cke': 'CKE', 'cfkg': 'CFKG', 'fm': 'fm', 'cofm': 'cofm'}
+REFERENCE_ONLY = ()                # every -model_type of the reference builds a model here
 MODEL_TYPES = ['transup', 'bprmf', 'fm', 'transe', 'transh', 'transr', 'transd', 'cfkg', 'cke', 'cofm', 'jtransup']
 DATASETS = ['ml1m', 'dbbook2014', 'amazon-book', 'last-fm', 'yelp2018']
 
 # (name, kind, default, help[, choices])
 FLAG_TABLE = [
-    ('model_type', 'enum', 'transup', 'which scorer to train / evaluate', MODEL_TYPES),
+    ('model_type', 'enum', 'transup', 'which scorer to train / evaluate (all eleven of the reference, transd included)', MODEL_TYPES),
     ('dataset', 'enum', 'ml1m', 'dataset directory under -data_path', DATASETS),
     ('optimizer_type', 'enum', 'Adagrad', 'torch.optim class', ['Adam', 'SGD', 'Adagrad', 'Rmsprop']),
     ('log_level', 'enum', 'debug', 'logging level', ['debug', 'info']),

@@ -1,4 +1,4 @@
-"""Knowledge-representation task driver (TransE / TransH / TransR) with the reference's entry points
+"""Knowledge-representation task driver (TransE / TransH / TransR / TransD) with the reference's entry points
 (jTransUP/models/knowledge_representation.py: evaluate :28-105, train_loop :107-219, run :221-310)."""
 import math
 import os
@@ -27,7 +27,7 @@ def evaluate(FLAGS, model, entity_total, relation_total, eval_head_iter, eval_ta
         ents = model.prepare_entities()
         head_fn, tail_fn = (lambda t, r: model.evaluateHead(t, r, ents=ents)), (lambda h, r: model.evaluateTail(h, r, ents=ents))
         kw = {'ents': ents}
-    # models with rank_entities (TransE, TransH, TransR): the whole pass -- scores and filtered gold ranks -- behind one call per direction
+    # models with rank_entities (TransE, TransH, TransR, TransD): the whole pass -- scores and filtered gold ranks -- behind one call per direction
     rank = (lambda head: (lambda q, r, desc, go, gi, fo, fi: model.rank_entities(q, r, head, desc, go, gi, fo, fi, **kw))) \
         if hasattr(model, 'rank_entities') else (lambda head: None)
     head_results = D.kg_eval_pass(FLAGS, head_fn, eval_head_iter, eval_head_dict, all_head_dicts, eval_descending,
@@ -57,10 +57,10 @@ def train_loop(FLAGS, model, trainer, train_dataset, eval_datasets, entity_total
     if FLAGS.filter_wrong_corrupted:
         all_head_dicts = [train_head_dict] + [d[4] for d in eval_datasets]
         all_tail_dicts = [train_tail_dict] + [d[5] for d in eval_datasets]
-    # TransE / TransH / TransR: the step body below as a handful of C-ABI launches (utils/fast_train.py KGStepper), optionally with the
+    # TransE / TransH / TransR / TransD: the step body below as a handful of C-ABI launches (utils/fast_train.py KGStepper), optionally with the
     # triples and the corruption sampling on the device (-device_sampling)
     stepper = feed = sampler = None
-    if D.USE_CUDA and FLAGS.model_type in ('transe', 'transh', 'transr') and trainer.fused is not None \
+    if D.USE_CUDA and FLAGS.model_type in ('transe', 'transh', 'transr', 'transd') and trainer.fused is not None \
             and os.environ.get('KTUP_FAST_TRAIN', '1') != '0':
         from jTransUP.utils.fast_train import DeviceFeeder, KGStepper
         stepper = KGStepper(model, trainer, FLAGS, FLAGS.batch_size)
@@ -75,7 +75,7 @@ def train_loop(FLAGS, model, trainer, train_dataset, eval_datasets, entity_total
             feed = DeviceFeeder(train_list, FLAGS.batch_size, D.DEV, FLAGS.negtive_samples, seed=FLAGS.seed)
             stepper.attach_feeds(sampler, kg=feed)
             logger.info('Training data and negative sampling are device-resident (-device_sampling).')
-    D.require_stepper_for_replicas(stepper, 'transe, transh, transr')
+    D.require_stepper_for_replicas(stepper, 'transe, transh, transr, transd')
     logger.info('Training.')
 
     def do_eval(totals):

@@ -633,8 +633,9 @@ class RecStepper(_StepperBase):
 
 
 class KGStepper(_StepperBase):
-    """KG-only driver (knowledge_representation.py:176-211) for TransE / TransH / TransR: marginLoss + normLoss(entity rows
-    of the positive and negative triples) + normLoss(relation rows) (+ orthogonalLoss(rel, norm) rows for TransH)."""
+    """KG-only driver (knowledge_representation.py:176-211) for TransE / TransH / TransR / TransD: marginLoss + normLoss(entity rows
+    of the positive and negative triples) + normLoss(relation rows) (+ orthogonalLoss(rel, norm) rows for TransH).  TransD's two
+    projection tables take the score gradient only (no regulariser touches them, knowledge_representation.py:200-204)."""
     KINDS = ('kg',)
     N_IDS = {'kg': 6}
 
@@ -642,8 +643,11 @@ class KGStepper(_StepperBase):
         model, B = self.m, self.B
         self.transh = hasattr(model, 'norm_embeddings')
         self.transr = hasattr(model, 'proj_embeddings')
+        self.transd = hasattr(model, 'ent_proj_embeddings')
         E, R = model.ent_embeddings.weight, model.rel_embeddings.weight
         self.tabs = (E, R, model.norm_embeddings.weight) if self.transh else (E, R, model.proj_embeddings.weight) if self.transr else (E, R)
+        if self.transd:
+            self.tabs = (E, R, model.ent_proj_embeddings.weight, model.rel_proj_embeddings.weight)
         if self.transr:             # scratch of the relation-bucketed forward (K4)
             nbytes = L.load().ktup_score_transr_workspace_bytes(2 * B, R.shape[0])
             self.rws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=self.dev)
@@ -655,7 +659,7 @@ class KGStepper(_StepperBase):
         d = E.shape[1]
         pos, neg, gpos, gneg = self.score[:B], self.score[B:], self.gscore[:B], self.gscore[B:]
         calls = []
-        self.fused_step = self._fused_ok(-1 if self.transr else (1 if self.transh else 2), d)      # (-1: no fused kernel; TransR's step stays multi-launch)
+        self.fused_step = self._fused_ok(-1 if (self.transr or self.transd) else (1 if self.transh else 2), d)      # (-1: no fused kernel; TransR's and TransD's steps stay multi-launch)
         if self.fused_step:
             Rn_ = self.tabs[2] if self.transh else None
             self._kg_fused = b('ktup_train_kg_step', int(self.transh), _p(E), E.stride(0), _p(R), R.stride(0), _p(Rn_),
@@ -671,6 +675,10 @@ class KGStepper(_StepperBase):
             M = self.tabs[2]
             calls.append(b('ktup_score_transr_fwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0), min(R.shape[0], M.shape[0]),
                            d, _p(self.h2), _p(self.t2), _p(self.r2), 2 * B, self.l1, _p(self.score), _p(self.rws), st))
+        elif self.transd:
+            Ep, Rp = self.tabs[2], self.tabs[3]
+            calls.append(b('ktup_score_transd_fwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(Ep), Ep.stride(0), _p(Rp), Rp.stride(0), d,
+                           _p(self.h2), _p(self.t2), _p(self.r2), 2 * B, self.l1, _p(self.score), st))
         else:
             calls.append(b('ktup_score_transe_fwd', _p(E), E.stride(0), _p(R), R.stride(0), R.shape[0], d, _p(self.h2), _p(self.t2), _p(self.r2),
                            2 * B, self.l1, _p(self.score), st))
@@ -683,6 +691,10 @@ class KGStepper(_StepperBase):
         elif self.transr:
             calls.append(b('ktup_score_transr_bwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0), d, _p(self.h2), _p(self.t2),
                            _p(self.r2), 2 * B, self.l1, _p(self.gscore), _p(E.grad), _p(R.grad), _p(M.grad), st))
+        elif self.transd:
+            calls.append(b('ktup_score_transd_bwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(Ep), Ep.stride(0), _p(Rp), Rp.stride(0), d,
+                           _p(self.h2), _p(self.t2), _p(self.r2), 2 * B, self.l1, _p(self.gscore), _p(E.grad), _p(R.grad), _p(Ep.grad),
+                           _p(Rp.grad), st))
         else:
             calls.append(b('ktup_score_transe_bwd', _p(E), E.stride(0), _p(R), R.stride(0), d, _p(self.h2), _p(self.t2), _p(self.r2),
                            2 * B, self.l1, _p(self.gscore), _p(E.grad), _p(R.grad), st))
