@@ -55,6 +55,8 @@ Option g_opts[] = {
     {"fwd_wide", "KTUP_FWD_WIDE", {env_int("KTUP_FWD_WIDE", 1)}},          // 0: K5-K7 forward at d = 256 keeps one wave per 16-pair tile for every batch size
     {"deterministic", "KTUP_DETERMINISTIC", {env_int("KTUP_DETERMINISTIC", 0)}},   // 1: ktup_train_rec_step / ktup_train_kg_step issue every gradient add from ONE workgroup in program order (parity runs: the same
                                                                             // bits on every run; ~1 ms per B = 512 step instead of ~0.02)
+    {"fwd_split", "KTUP_FWD_SPLIT", {env_int("KTUP_FWD_SPLIT", 1)}},       // 0: K5-K7 soft-gate forward keeps its r / n contractions on the fp32 matrix pipe (1: three bf16 pieces, six products,
+                                                                            // on v_mfma_f32_16x16x32_bf16 where the geometry allows: ktup_score_pref_mc.hip)
 };
 Option* find(const char* name) {
   for (auto& o : g_opts)
@@ -78,6 +80,7 @@ int opt_kg_exact() { return g_opts[12].value.load(std::memory_order_relaxed); }
 int opt_wide_waves() { return g_opts[13].value.load(std::memory_order_relaxed); }
 int opt_fwd_wide() { return g_opts[14].value.load(std::memory_order_relaxed); }
 int opt_deterministic() { return g_opts[15].value.load(std::memory_order_relaxed); }
+int opt_fwd_split() { return g_opts[16].value.load(std::memory_order_relaxed); }
 
 // A library-owned second stream for work that depends only on a call's INPUTS (the counting sorts of the segment reductions)
 // while the caller's stream runs the kernel that produces the data: fork_side makes it wait for everything enqueued on `st` so far,

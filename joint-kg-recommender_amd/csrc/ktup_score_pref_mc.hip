@@ -19,6 +19,24 @@
 //   * x / q / distance math on <4 x float> values -> v_pk_add_f32 / v_pk_fma_f32;
 //   * when the last 16-slot preference tile holds <= 4 preferences (P = 20), its logits come from
 //     v_mfma_f32_4x4x1_16B_f32 (16 blocks = 4 pair groups x 4 k-quarters, 8 clk each) instead of a 3/4-empty 16x16x4.
+//
+// Split stage 2 (McGeom<.., SPLIT = true>, option fwd_split, soft gate, d <= 128): the two contractions over the preferences,
+// r^T = Ar^T . logits^T and n^T = Cn^T . logits^T, are most of the fp32 MFMA clocks of a tile (2 NP 32-clock instructions per
+// 16-coordinate tile).  They run on v_mfma_f32_16x16x32_bf16 instead (16 clk, K = 32 preference slots in one instruction) with
+// fp32-grade products: both operands are split into three bf16 pieces hi + mid + lo == x (exactly), every bf16 x bf16 product is exact
+// in the fp32 accumulator, and the six products hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi keep every term above 2^-24 of the full
+// product -- 6 x 16 clk per tile and table whatever P is, against NP x 32.
+//   * tables: Cn and Ar are split ONCE per workgroup while they are staged, into three bf16 planes each, [coordinate][k-quarter][8 slots]:
+//     lane (kq, j) reads the A operand A[row = coordinate 16 ct + j][k = 8 kq + s] of a piece as one ds_read_b128.  The fp32 copies of
+//     the two tables are not staged at all;
+//   * logits: slot k = 8 kq + s is preference 4 s + kq = the logit register lg[s >> 2][s & 3] lane (kq, pair) holds after stage 1 (which
+//     stays on the fp32 pipe: three bf16 planes of the x tile per wave do not fit the LDS), so the B operand is split in registers
+//     (v_cvt_pk_bf16_f32 + a subtraction per level) and never passes through the LDS;
+//   * C / D of the 16x16x32 form is laid out like the fp32 form's (row = 4 kq + reg, column = pair): the epilogue (s = q . n,
+//     q + r - s n, the distance) is the fp32 kernel's, and accR still starts at q;
+//   * d = 100: the last 4 coordinates are a seventh (mostly zero) tile instead of the fp32 kernel's 4x4x1 blocks + reduce-scatter.
+// Used where it is fewer matrix clocks (NP >= 4) and the planes (3 x 64 B per coordinate and table) leave the workgroup as many waves
+// as the fp32 tables: d = 64 (8 < P <= 32), d = 100 (8 < P <= 20), d = 128 (16 < P <= 20).  fwd_split = 0 runs the fp32 stage 2 everywhere.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -31,10 +49,37 @@
 namespace ktup {
 namespace {
 
-template <int NCH_, int NP_, bool HASE_, bool HARD_>
+// ---- split stage 2: an fp32 value as three bf16 pieces.  hi = bf16(x), mid = bf16(x - hi), lo = x - hi - mid (round to nearest each
+// time): both differences are exact in fp32 and the last one has at most 8 significant bits, so hi + mid + lo == x.
+typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
+typedef float f8 __attribute__((ext_vector_type(8)));
+struct Split3 { bf8 hi, mid, lo; };
+KTUP_DEV Split3 split3(const f8 x) {
+  Split3 r;
+  r.hi = __builtin_convertvector(x, bf8);
+  const f8 r1 = x - __builtin_convertvector(r.hi, f8);
+  r.mid = __builtin_convertvector(r1, bf8);
+  const f8 r2 = r1 - __builtin_convertvector(r.mid, f8);
+  r.lo = __builtin_convertvector(r2, bf8);
+  return r;
+}
+// table . logits over 32 preference slots with fp32-grade products: every bf16 x bf16 product is exact in the fp32 accumulator, and the
+// six kept ones hold every term above 2^-24 of the full product (dropped: mid.lo, lo.mid, lo.lo); smallest terms first
+KTUP_DEV v4 mfma_split(const bf8 ah, const bf8 am, const bf8 al, const Split3& b, v4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b.lo, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, b.hi, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, b.mid, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b.mid, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, b.hi, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b.hi, acc, 0, 0, 0);
+}
+
+template <int NCH_, int NP_, bool HASE_, bool HARD_, bool SPLIT_ = false>
 struct McGeom {
   static constexpr int NCH = NCH_, NP = NP_;
   static constexpr bool HASE = HASE_, HARD = HARD_;   // HARD: straight-through Gumbel gate (forward value = one-hot)
+  static constexpr bool SPLIT = SPLIT_;               // soft gate: stage 2 on v_mfma_f32_16x16x32_bf16, operands as three bf16 pieces
+  static_assert(!(SPLIT && HARD) && !(SPLIT && NP > 8), "the split stage 2 is the soft gate's, K = 32 preference slots");
   static constexpr int D = 4 * NCH;
   static constexpr int KG = (D + 15) / 16;               // stage-1 k groups of 16 coordinates
   static constexpr int CT = KG;                          // stage-2 coordinate tiles of 16
@@ -44,7 +89,8 @@ struct McGeom {
   static constexpr int PTF = REM4 ? PT - 1 : PT;         // tiles computed with 16x16x4
   static constexpr bool TAIL1 = NCH - 4 * (KG - 1) == 1;  // the last k group / coordinate tile holds ONE float4 chunk (d = 100):
   static constexpr int KGF = TAIL1 ? KG - 1 : KG;        //   stage 1 finishes with one b32-operand MFMA instead of four,
-  static constexpr int CTF = TAIL1 ? CT - 1 : CT;        //   stage 2 does those 4 coordinates with 4x4x1 MFMAs
+  static constexpr bool TAIL2 = TAIL1 && !SPLIT;         //   stage 2 does those 4 coordinates with 4x4x1 MFMAs -- the split stage 2
+  static constexpr int CTF = TAIL2 ? CT - 1 : CT;        //   takes them as one more 16-coordinate tile (6 x 16 clk against 2 NP x 8 + a scatter)
   static constexpr int J = (16 * NCH + 63) / 64;         // float4 loads per lane, table and tile
   static constexpr int TOTAL = 16 * NCH;
   static constexpr int PITCHA4 = 4 * KG + 1;             // odd float4 pitch of the slot-ordered logit table
@@ -54,7 +100,8 @@ struct McGeom {
   static constexpr int A_F4 = PTF * 16 * PITCHA4;        // float4s of the 16x16x4 logit table
   static constexpr int A4_F4 = REM4 ? 4 * 4 * KQ : 0;    // REM4 table: [4 prefs][4 quarters][KQ] float4
   static constexpr int HP = NCH | 1;                     // HARD: odd float4 pitch of the row-major tables (one row is looked up per pair)
-  static constexpr int T_F = HARD ? TROW * HP * 4 : TROW * TPITCH;   // floats per stage-2 table
+  static constexpr int PLANE_Q = 16 * CT * 4;            // SPLIT: 16-byte chunks of one bf16 plane, [16 CT coordinates][4 k-quarters] x 8 slots
+  static constexpr int T_F = SPLIT ? 3 * PLANE_Q * 4 : HARD ? TROW * HP * 4 : TROW * TPITCH;   // floats per stage-2 table (SPLIT: three planes)
   static constexpr size_t TABLE_BYTES = (size_t)(A_F4 + A4_F4) * 16 + (size_t)2 * T_F * 4;
   static constexpr int XT_F4 = 16 * NCH + 3;             // x / q tile + 3 zero chunks (stage-1 reads run past the last row)
   static constexpr int NOISE_F = HARD ? 16 * TROW : 0;   // HARD: Gumbel noise of the tile, [pair][preference]
@@ -85,7 +132,8 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
   KTUP_RESOLVE_GUMBEL(a);
   constexpr int NCH = G::NCH, NP = G::NP, KG = G::KG, CT = G::CT, PTF = G::PTF, J = G::J, TOTAL = G::TOTAL;
   constexpr int PITCHA4 = G::PITCHA4, TPITCH = G::TPITCH, KQ = G::KQ;
-  constexpr bool HASE = G::HASE, REM4 = G::REM4, TAIL1 = G::TAIL1, HARD = G::HARD;
+  constexpr bool HASE = G::HASE, REM4 = G::REM4, TAIL1 = G::TAIL1, HARD = G::HARD, SPLIT = G::SPLIT, TAIL2 = G::TAIL2;
+  constexpr int PLQ = G::PLANE_Q;
   constexpr int HP = G::HP;
   constexpr int KGF = G::KGF, CTF = G::CTF;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -120,7 +168,31 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
         A4S[idx] = (p < P && c < NCH) ? *reinterpret_cast<const v4*>(a.Alog + p * dp + 4 * c) : zero;
       }
     }
-    {
+    if constexpr (SPLIT) {
+      // three bf16 planes per table, [coordinate c][k-quarter][8 slots]: lane (kq, j) of the 16x16x32 MFMA reads the A operand of
+      // coordinate 16 ct + j as ONE 16-byte chunk.  Slot (kq, s) = preference 4 s + kq = 16 tt + 4 reg + kq with s = 4 tt + reg: the
+      // preferences whose logits lg[tt][reg] lane (kq, .) holds after stage 1.  The chunks of coordinates with bit 3 set sit two places on
+      // (kq ^ 2): a 16-lane group of ds_read_b128 is rows {0-3, 12-15} of one quarter + rows 4-11 of the next, and rows 8 apart
+      // (64-byte rows) would share their banks.
+      bf8* CnP = reinterpret_cast<bf8*>(CnS);
+      bf8* ArP = reinterpret_cast<bf8*>(ArS);
+      constexpr int NC = 16 * CT;
+      for (int idx = t; idx < 4 * NC; idx += nthr) {
+        const int kqs = idx / NC, c = idx - kqs * NC;
+        f8 vn, vr;
+#pragma unroll
+        for (int sl = 0; sl < 8; ++sl) {
+          const int p = 4 * sl + kqs;
+          const bool ok = p < P && c < 4 * NCH;
+          vn[sl] = ok ? a.Cn[p * dp + c] : 0.f;
+          vr[sl] = ok ? a.Ar[p * dp + c] : 0.f;
+        }
+        const Split3 sn = split3(vn), sr = split3(vr);
+        const int o = 4 * c + (kqs ^ ((c >> 2) & 2));
+        CnP[o] = sn.hi; CnP[PLQ + o] = sn.mid; CnP[2 * PLQ + o] = sn.lo;
+        ArP[o] = sr.hi; ArP[PLQ + o] = sr.mid; ArP[2 * PLQ + o] = sr.lo;
+      }
+    } else {
       constexpr int pitch4 = HARD ? HP : TPITCH / 4;
       v4* Cn4 = reinterpret_cast<v4*>(CnS);
       v4* Ar4 = reinterpret_cast<v4*>(ArS);
@@ -148,6 +220,8 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
   const v4* tab = AlogS + j * PITCHA4 + kq;                      // stage-1 A operand
   const float* tn0 = CnS + kq * TPITCH + j;
   const float* tr0 = ArS + kq * TPITCH + j;
+  const bf8* pn0 = reinterpret_cast<const bf8*>(CnS) + 4 * j + (kq ^ ((j >> 2) & 2));   // SPLIT: this lane's chunk of coordinate j, plane hi
+  const bf8* pr0 = reinterpret_cast<const bf8*>(ArS) + 4 * j + (kq ^ ((j >> 2) & 2));
   constexpr bool l1 = L1;
   const int64_t ntiles = (a.n + 15) / 16;
   const int64_t wstride = (int64_t)gridDim.x * nwr;
@@ -157,9 +231,13 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
     // six registers the kernel had to spill at 128 -- with scratch reloads in front of the id loads and inside the matrix phases
     const int64_t row0 = tile_id * 16;
     const int rem = (int)(a.n - row0 < 16 ? a.n - row0 : 16);
+    // SPLIT: the id loads index with a per-tile opaque copy of the lane number -- hoisted out of the tile loop, the 64-bit byte offset
+    // of the lane is the register pair that tips this kernel over 128 (it was spilled, and reloaded in front of every id load)
+    int idl = lane;
+    if constexpr (SPLIT) asm volatile("" : "+v"(idl));
     if (first && lane < 16) {
       const bool ok = lane < rem;
-      const int64_t uid = ok ? (a.u_ids + row0)[lane] : 0, iid = ok ? (a.i_ids + row0)[lane] : 0;
+      const int64_t uid = ok ? (a.u_ids + row0)[idl] : 0, iid = ok ? (a.i_ids + row0)[idl] : 0;
       sid[lane] = (int32_t)uid;
       sid[16 + lane] = (int32_t)iid;
       sid[32 + lane] = HASE ? a.item2ent[iid] : 0;
@@ -211,7 +289,7 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
     if (pre) {
       const int64_t row1 = (tile_id + wstride) * 16;
       const bool ok = lane < a.n - row1;
-      const int64_t uid = ok ? (a.u_ids + row1)[lane] : 0, iid = ok ? (a.i_ids + row1)[lane] : 0;
+      const int64_t uid = ok ? (a.u_ids + row1)[idl] : 0, iid = ok ? (a.i_ids + row1)[idl] : 0;
       nx_u = (int32_t)uid; nx_i = (int32_t)iid;
       nx_e = HASE ? a.item2ent[iid] : 0;
     }
@@ -356,6 +434,16 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
     __builtin_amdgcn_wave_barrier();
     // ---- stage 2a: n^T coordinate tiles
     v4 accN[CTF];
+    Split3 lgs;                                                  // SPLIT: B[k = 8 kq + s][pair j] = the logit registers in hand, in pieces
+    if constexpr (SPLIT) {
+      f8 g;
+#pragma unroll
+      for (int sl = 0; sl < 8; ++sl) g[sl] = (sl >> 2) < G::PT ? lg[(sl >> 2) < G::PT ? sl >> 2 : 0][sl & 3] : 0.f;
+      lgs = split3(g);
+#pragma unroll
+      for (int ct = 0; ct < CTF; ++ct)
+        accN[ct] = mfma_split(pn0[64 * ct], pn0[PLQ + 64 * ct], pn0[2 * PLQ + 64 * ct], lgs, (v4){0.f, 0.f, 0.f, 0.f});
+    } else {
 #pragma unroll
     for (int ct = 0; ct < CTF; ++ct) {
       accN[ct] = (v4){0.f, 0.f, 0.f, 0.f};
@@ -365,11 +453,12 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
 #pragma unroll
       for (int m = 0; m < NP; ++m) accN[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(ta[m], lg[m >> 2][m & 3], accN[ct], 0, 0, 0);
     }
+    }
     // TAIL1: the last 4 coordinates c0 + i (c0 = 16 CTF) on 4x4x1 blocks.  Block (kq, pair group): A row i = T[kq + 4 s][c0 + i],
     // B column = logit(kq + 4 s, pair) = lg[s >> 2][s & 3] of THIS lane, k step s.  n4 / r4 of lane (kq, pair) are partial
     // over the NP preferences {kq + 4 s}; the sum over kq comes with the s reduction (linear) or a reduce-scatter (distance).
     v4 n4 = (v4){0.f, 0.f, 0.f, 0.f}, r4 = n4, q4 = n4;
-    if (TAIL1) {
+    if (TAIL2) {
       const float* tn4 = CnS + kq * TPITCH + 16 * CTF + (lane & 3);
       const float* tr4 = ArS + kq * TPITCH + 16 * CTF + (lane & 3);
       float tan[NP], tar[NP];
@@ -383,7 +472,7 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
       q4 = xt[j * NCH + 4 * CTF];                                // q chunk of coordinates c0 .. c0 + 3 (same for the 4 kq lanes)
     }
     // ---- s = q . n   (lane (kq, j) owns coordinates 16 ct + 4 kq .. + 3 = q chunk 4 ct + kq of pair j)
-    v4 sacc = TAIL1 ? q4 * n4 : (v4){0.f, 0.f, 0.f, 0.f};
+    v4 sacc = TAIL2 ? q4 * n4 : (v4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ct = 0; ct < CTF; ++ct) {
       if (4 * ct + 3 < NCH) {
@@ -398,8 +487,10 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
 #pragma unroll
     for (int ct = 0; ct < CTF; ++ct) {
       float ta[NP];
+      if constexpr (!SPLIT) {
 #pragma unroll
-      for (int m = 0; m < NP; ++m) ta[m] = tr0[(16 * (m >> 2) + 4 * (m & 3)) * TPITCH + 16 * ct];
+        for (int m = 0; m < NP; ++m) ta[m] = tr0[(16 * (m >> 2) + 4 * (m & 3)) * TPITCH + 16 * ct];
+      }
       v4 qv = (v4){0.f, 0.f, 0.f, 0.f};
       if (4 * ct + 3 < NCH) {
         qv = xb[4 * ct];
@@ -407,13 +498,17 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
         if (4 * ct + kq < NCH) qv = xb[4 * ct];
       }
       v4 accR = qv;                                              // q + r: start the accumulator at q
+      if constexpr (SPLIT) {
+        accR = mfma_split(pr0[64 * ct], pr0[PLQ + 64 * ct], pr0[2 * PLQ + 64 * ct], lgs, accR);
+      } else {
 #pragma unroll
-      for (int m = 0; m < NP; ++m) accR = __builtin_amdgcn_mfma_f32_16x16x4f32(ta[m], lg[m >> 2][m & 3], accR, 0, 0, 0);
+        for (int m = 0; m < NP; ++m) accR = __builtin_amdgcn_mfma_f32_16x16x4f32(ta[m], lg[m >> 2][m & 3], accR, 0, 0, 0);
+      }
       const v4 tv = __builtin_elementwise_fma(ms, accN[ct], accR);
       if (l1) dacc += __builtin_elementwise_abs(tv);
       else dacc = __builtin_elementwise_fma(tv, tv, dacc);
     }
-    if (TAIL1) {                                                 // lane kq takes coordinate c0 + kq
+    if (TAIL2) {                                                 // lane kq takes coordinate c0 + kq
       const float nf = scatter_kq(n4), rf = scatter_kq(r4);
       const float qe = kq == 0 ? q4[0] : kq == 1 ? q4[1] : kq == 2 ? q4[2] : q4[3];
       const float tv = fmaf(-sfull, nf, qe + rf);
@@ -706,6 +801,15 @@ int launch_mc_e(const McArgs& a, hipStream_t st, const char* name) {
   if (a.gumbel != KTUP_GUMBEL_OFF) {
     if (a.E) return launch_mc<McGeom<NCH, NP, true, true>>(a, st, name);
     return launch_mc<McGeom<NCH, NP, false, true>>(a, st, name);
+  }
+  // option fwd_split: stage 2 on the bf16 matrix pipe, where that is fewer clocks (NP >= 4: six 16-clock MFMAs per tile and table
+  // against NP 32-clock ones) and the three bf16 planes leave the workgroup as many waves as the fp32 tables do
+  if constexpr (NCH <= 32 && NP >= 4 && McGeom<NCH, NP, true, false, true>::NW == McGeom<NCH, NP, true, false>::NW &&
+                McGeom<NCH, NP, false, false, true>::NW == McGeom<NCH, NP, false, false>::NW) {
+    if (opt_fwd_split()) {
+      if (a.E) return launch_mc<McGeom<NCH, NP, true, false, true>>(a, st, name);
+      return launch_mc<McGeom<NCH, NP, false, false, true>>(a, st, name);
+    }
   }
   if (a.E) return launch_mc<McGeom<NCH, NP, true, false>>(a, st, name);
   return launch_mc<McGeom<NCH, NP, false, false>>(a, st, name);
