@@ -175,6 +175,13 @@ SIGNATURES_TRANSD = {
 }
 _RESTYPE.update({'ktup_eval_transd_workspace_bytes': ctypes.c_size_t, 'ktup_eval_kg_ranks_transd_workspace_bytes': ctypes.c_size_t})
 
+# The inner-product evaluation pass (include/ktup_dot.h; kernels under csrc/dot/, same library): a table of its own for the same reason.
+SIGNATURES_DOT = {
+    'ktup_eval_dot_topk_workspace_bytes': [c_i, c_l, c_l, c_i, c_i],
+    'ktup_eval_dot_topk': [c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
+}
+_RESTYPE.update({'ktup_eval_dot_topk_workspace_bytes': ctypes.c_size_t})
+
 _lib = None
 
 
@@ -194,7 +201,7 @@ def load():
         raise KtupError('libktup_hip.so not found at %s -- build it with '
                         '`python joint-kg-recommender_amd/build_hip.py` (there is no CPU fallback)' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_TRANSD.items()):
+    for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_TRANSD.items()) + list(SIGNATURES_DOT.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, ctypes.c_int)

@@ -829,6 +829,43 @@ def eval_pref_topk_hard(U, u, items, l1, topn, gumbel_mode, uniform=None, seed=0
     return (top, ts) if with_scores else top
 
 
+@torch.no_grad()
+def eval_dot_topk(U, I, u, topn, filt_off=None, filt_ids=None, user_add=None, item_add=None, with_scores=False, nsplit=0):
+    """Scores + filtered top-n of a whole evaluation pass of the inner-product recommenders in one sweep (ktup_eval_dot_topk):
+    score(b, j) = (U[u_b] . I[j] + user_add[b]) + item_add[j] for every user of `u` against all rows of `I`, no (users x items)
+    matrix; the bits and the order of eval_bprmf + the two adds + topk_filtered(descending=True).  user_add: (len(u),) fp32, item_add:
+    (n_items,) fp32, either may be None.  -> int32 (len(u), topn) ids (-1 padded) [, scores], or None where the entry point declines
+    the shape (topn > 16, d > 256): keep the per-batch calls."""
+    dev = _dev(_table('user table', U)); _table('item table', I)
+    if I.device != dev or I.shape[1] != U.shape[1]:
+        raise L.KtupError('user and item tables must share the device and the embedding size')
+    u = _ids('u_ids', u, dev)
+    nq, d, ni = u.numel(), U.shape[1], I.shape[0]
+
+    def _term(name, t, n):
+        if t is None:
+            return None
+        if t.device != dev or t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n:
+            raise L.KtupError('%s must be a 1-D fp32 tensor of %d entries on %s' % (name, n, dev))
+        return t.detach().contiguous()
+    user_add, item_add = _term('user_add', user_add, nq), _term('item_add', item_add, ni)
+    if not (0 < topn <= 16) or nq == 0 or ni == 0 or not (0 < d <= 256):
+        return None
+    if filt_ids is not None and filt_ids.numel() == 0:       # an empty id list has no storage to point at: same as no filter
+        filt_off = filt_ids = None
+    top = torch.empty(nq, topn, dtype=torch.int32, device=dev)
+    ts = torch.empty(nq, topn, dtype=torch.float32, device=dev) if with_scores else None
+    ws = _scratch(L.load().ktup_eval_dot_topk_workspace_bytes(d, nq, ni, int(topn), int(nsplit)), dev)
+    try:
+        L.call('ktup_eval_dot_topk', _p(U), U.stride(0), _p(I), I.stride(0), d, _p(u), nq, ni, _p(user_add), _p(item_add), _p(filt_off),
+               _p(filt_ids), int(topn), int(nsplit), _p(top), _p(ts), _p(ws), _stream(dev))
+    except L.KtupError as e:
+        if e.code == L.ERR_UNSUPPORTED:
+            return None
+        raise
+    return (top, ts) if with_scores else top
+
+
 def eval_tup(U, I, pref, pref_norm, u, l1, gumbel_mode=GUMBEL_OFF, uniform=None, seed=0, offset=0, items=None):
     """transUP.py:84-102 -> (len(u), n_items).  `items`: eval_pref_items(...) of the same tables (one per evaluation pass)."""
     return _eval_pref(U, I, None, pref, pref_norm, None, None, None, u, l1, gumbel_mode, uniform, seed, offset, items)

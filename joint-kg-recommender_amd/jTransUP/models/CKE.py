@@ -73,6 +73,15 @@ class CKE(nn.Module, GradToggle):
         with torch.no_grad():
             return ops.eval_bprmf(self.user_embeddings.weight, self._item_side().contiguous(), u_ids)
 
+    topk_descending = True                 # a higher score ranks first (the drivers' eval_descending for this model)
+
+    def evaluate_topk(self, u_ids, items, topn, filt_off=None, filt_ids=None):
+        """`evaluateRec` + the filtered top-n for a whole evaluation pass in one sweep (this build), no (users x items) matrix.  The
+        item side (item + aligned entity rows) is built inside the call, so a captured pass recomputes it from the tables.  `items`
+        is unused; None where the sweep declines."""
+        with torch.no_grad():
+            return ops.eval_dot_topk(self.user_embeddings.weight, self._item_side().contiguous(), u_ids, topn, filt_off, filt_ids)
+
     def prepare_entities(self):
         """Entity side of evaluateHead / evaluateTail, once per evaluation pass (`ents=`)."""
         return ops.eval_transr_entities(self.ent_embeddings.weight, self.proj_embeddings.weight, self.rel_embeddings.weight.shape[0], self.L1_flag)

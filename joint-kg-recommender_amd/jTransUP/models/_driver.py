@@ -277,14 +277,17 @@ def _rec_eval_fused(FLAGS, pass_fn, eval_iter, index, graph_key=None):
     return _present_rows(_to_host(entry[1], copy=False), index)     # the copy back stays outside the graph (a copy node: 0.5 ms)
 
 
-def rec_eval_pass(FLAGS, score_fn, eval_iter, eval_dict, all_dicts, descending, want_rows=True, shard=None, pass_fn=None, graph_key=None):
+def rec_eval_pass(FLAGS, score_fn, eval_iter, eval_dict, all_dicts, descending, want_rows=True, shard=None, pass_fn=None, graph_key=None,
+                  pass_descending=False):
     """One pass over the evaluation users: all-item scores, filtered top-n, metric rows (misc.py:148-248 semantics).
     want_rows=False returns the (n x 5) metric array only (no per-user report rows).  Under torchrun the batches are
-    dealt round-robin to the ranks and the results gathered, so every rank reports the same numbers."""
+    dealt round-robin to the ranks and the results gathered, so every rank reports the same numbers.
+    pass_descending: the order `pass_fn` ranks in (a model's `topk_descending`: False = lower score first, the translation
+    models; True = the inner-product models); the whole-pass route is taken only where it is the order asked for."""
     index = rank_index(eval_iter, eval_dict, all_dicts)
     if _shard_mode(FLAGS, shard, want_rows):
         return _rec_eval_sharded(FLAGS, shard, eval_iter, index, descending)
-    if pass_fn is not None and not want_rows and not descending and os.environ.get('KTUP_EVAL_PASS', '1') != '0':
+    if pass_fn is not None and not want_rows and bool(descending) == bool(pass_descending) and os.environ.get('KTUP_EVAL_PASS', '1') != '0':
         fused = _rec_eval_fused(FLAGS, pass_fn, eval_iter, index, graph_key)      # every rank runs the whole pass: ~0.3 ms at ml1m size
         if fused is not None:
             return fused

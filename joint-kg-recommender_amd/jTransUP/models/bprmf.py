@@ -29,3 +29,11 @@ class BPRMF(nn.Module, GradToggle):
     def evaluate(self, u_ids):
         """K11: all-item scores U[u] . I^T (bprmf.py:51-54)."""
         return ops.eval_bprmf(self.user_embeddings.weight, self.item_embeddings.weight, u_ids)
+
+    topk_descending = True                 # a higher score ranks first (the drivers' eval_descending for this model)
+
+    def evaluate_topk(self, u_ids, items, topn, filt_off=None, filt_ids=None):
+        """K11 + K17 for a whole evaluation pass in one sweep (this build): filtered top-n item ids of every user of `u_ids`
+        without the (users x items) matrix; the scores and the order are `evaluate`'s + topk_filtered's, bit for bit.  `items` is
+        unused (this model has no prepared item side); None where the sweep declines (topn > 16, embedding_size > 256)."""
+        return ops.eval_dot_topk(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, topn, filt_off, filt_ids)

@@ -58,6 +58,19 @@ class coFM(nn.Module, GradToggle):
         gemm = ops.eval_bprmf(self.user_embeddings.weight, all_i, u_ids)
         return gemm + (self.bias + self.user_bias(u_ids))[:, None] + all_b[None, :]
 
+    topk_descending = True                 # a higher score ranks first (the drivers' eval_descending for this model)
+
+    def evaluate_topk(self, u_ids, items, topn, filt_off=None, filt_ids=None):
+        """`evaluateRec` + the filtered top-n for a whole evaluation pass in one sweep (this build), own item table only: with
+        shared tables the candidates are the item ids' rows of the entity table (all_i_ids) and the batch walk stays -> None.  The
+        bias terms are formed by torch exactly as `evaluateRec` forms them.  `items` is unused; None where the sweep declines."""
+        if self.is_share:
+            return None
+        with torch.no_grad():
+            user_add = self.bias + self.user_bias(u_ids)
+            return ops.eval_dot_topk(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, topn, filt_off, filt_ids,
+                                     user_add=user_add, item_add=self.item_bias.weight)
+
     def _cand(self, all_e_ids):
         return self.ent_embeddings(all_e_ids).detach().contiguous() if (all_e_ids is not None and self.is_share) else None
 

@@ -48,3 +48,14 @@ class FM(nn.Module, GradToggle):
         """fm.py:69-80: (len(u), item_total); the GEMM is K11."""
         gemm = ops.eval_bprmf(self.user_embeddings.weight, self.item_embeddings.weight, u_ids)
         return gemm + (self.bias + self.user_bias(u_ids))[:, None] + self.item_bias.weight[None, :]
+
+    topk_descending = True                 # a higher score ranks first (the drivers' eval_descending for this model)
+
+    def evaluate_topk(self, u_ids, items, topn, filt_off=None, filt_ids=None):
+        """`evaluate` + the filtered top-n for a whole evaluation pass in one sweep (this build), no (users x items) matrix: the
+        user-side and item-side bias terms are formed by torch exactly as `evaluate` forms them and added to the dot product in its
+        order, so scores and order are the per-batch route's bits.  `items` is unused; None where the sweep declines."""
+        with torch.no_grad():
+            user_add = self.bias + self.user_bias(u_ids)
+            return ops.eval_dot_topk(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, topn, filt_off, filt_ids,
+                                     user_add=user_add, item_add=self.item_bias.weight)

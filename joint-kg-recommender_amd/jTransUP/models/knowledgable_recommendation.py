@@ -57,14 +57,16 @@ def evaluateRec(FLAGS, model, eval_iter, eval_dict, all_dicts, i_map, logger, ev
         return model.evaluateRec(u, all_i_ids=all_i_var, items=lazy[0])
     from jTransUP.models._shard_eval import rec_shard_fn
     # the whole-pass route prepares its own item side, so that a captured pass (D._rec_eval_fused) recomputes it from the tables
-    pass_fn = (lambda u, fo, fi, n: model.evaluate_topk(u, model.prepare_items(), n, fo, fi)) \
-        if has_items and hasattr(model, 'evaluate_topk') and not FLAGS.share_embeddings else None
+    # (KTUP prepares an item side; the inner-product models -- CKE, coFM -- have none and sweep their tables as they are)
+    pass_fn = (lambda u, fo, fi, n: model.evaluate_topk(u, model.prepare_items() if has_items else None, n, fo, fi)) \
+        if hasattr(model, 'evaluate_topk') and not FLAGS.share_embeddings else None
     native = getattr(model, '_shard_native', None)             # -shard_tables: the candidates are the rows this rank owns
     if native is not None and not is_report:
         results = D.rec_eval_pass(FLAGS, None, eval_iter, eval_dict, all_dicts, eval_descending, want_rows=False, shard=native.rec_shard())
     else:
         results = D.rec_eval_pass(FLAGS, score_fn, eval_iter, eval_dict, all_dicts, eval_descending, want_rows=is_report,
-                                  shard=rec_shard_fn(model), pass_fn=pass_fn, graph_key=D.model_graph_key(model) if pass_fn else None)
+                                  shard=rec_shard_fn(model), pass_fn=pass_fn, graph_key=D.model_graph_key(model) if pass_fn else None,
+                                  pass_descending=getattr(model, 'topk_descending', False))
     perf = D.summarize_rec(FLAGS, results, logger)
     if is_report:
         D.report_rec(FLAGS, model, results, all_dicts, eval_dict, logger, FLAGS.model_type in ('transup', 'jtransup'))

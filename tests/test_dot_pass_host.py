@@ -1,0 +1,103 @@
+"""The inner-product evaluation pass without a GPU: the extension header against the built library and the binding table, the
+models' and the driver's surface, and host-side argument validation of the new entry point (no launch is made)."""
+import ctypes
+import inspect
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, 'include', 'ktup_hip.h')
+HEADER_DOT = os.path.join(ROOT, 'include', 'ktup_dot.h')
+ERR_INVALID, ERR_UNSUPPORTED = -1, -3
+
+
+def declared_symbols(path):
+    text = open(path).read()
+    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    return sorted(set(re.findall(r'\b(ktup_[a-z0-9_]+)\s*\(', text)))
+
+
+@pytest.fixture(scope='module')
+def lib():
+    from jTransUP.hip import lib as L
+    if not os.path.exists(L.LIB_PATH):
+        import importlib.util
+        spec = importlib.util.spec_from_file_location('build_hip', os.path.join(ROOT, 'joint-kg-recommender_amd', 'build_hip.py'))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        mod.build(verbose=False)
+    return L
+
+
+def test_extension_header_library_and_binding_table_agree(lib):
+    syms = declared_symbols(HEADER_DOT)
+    assert syms == ['ktup_eval_dot_topk', 'ktup_eval_dot_topk_workspace_bytes']
+    handle = ctypes.CDLL(lib.LIB_PATH)
+    missing = [s for s in syms if not hasattr(handle, s)]
+    assert not missing, 'declared in include/ktup_dot.h but not exported: %s' % missing
+    assert sorted(lib.SIGNATURES_DOT) == syms
+    assert sorted(lib.SIGNATURES) == declared_symbols(HEADER)            # the first table still mirrors the first header
+    assert not set(lib.SIGNATURES) & set(lib.SIGNATURES_DOT) and not set(lib.SIGNATURES_TRANSD) & set(lib.SIGNATURES_DOT)
+    loaded = lib.load()
+    for s in syms:
+        assert getattr(loaded, s).argtypes == lib.SIGNATURES_DOT[s]
+    assert loaded.ktup_eval_dot_topk_workspace_bytes.restype is ctypes.c_size_t
+    # the partial lists of the splits (8 bytes a key) and one filter bit per (user, item)
+    one = loaded.ktup_eval_dot_topk_workspace_bytes(64, 100, 3240, 10, 1)
+    assert one >= 100 * 10 * 8 + 100 * ((3240 + 31) // 32) * 4
+    assert loaded.ktup_eval_dot_topk_workspace_bytes(64, 100, 3240, 10, 4) >= one + 100 * 10 * 8 * 3
+    assert loaded.ktup_eval_dot_topk_workspace_bytes(64, 100, 3240, 10, 0) >= one
+    assert loaded.ktup_eval_dot_topk_workspace_bytes(64, 0, 3240, 10, 0) == 0
+    assert loaded.ktup_eval_dot_topk_workspace_bytes(64, 100, 3240, 17, 0) == 0
+
+
+def test_models_and_driver_surface():
+    from jTransUP.models import CKE, _driver, bprmf, cofm, fm
+    for cls in (bprmf.BPRMF, fm.FM, CKE.CKE, cofm.coFM):
+        assert callable(getattr(cls, 'evaluate_topk')), cls
+        assert list(inspect.signature(cls.evaluate_topk).parameters) == ['self', 'u_ids', 'items', 'topn', 'filt_off', 'filt_ids'], cls
+        assert cls.topk_descending is True, cls
+        assert not hasattr(cls, 'prepare_items'), cls          # both drivers key the TUP item-side cache and `items=` on it
+    par = inspect.signature(_driver.rec_eval_pass).parameters
+    assert 'pass_descending' in par and par['pass_descending'].default is False
+    from jTransUP.hip import ops
+    par = inspect.signature(ops.eval_dot_topk).parameters
+    assert list(par) == ['U', 'I', 'u', 'topn', 'filt_off', 'filt_ids', 'user_add', 'item_add', 'with_scores', 'nsplit']
+    assert par['nsplit'].default == 0 and par['with_scores'].default is False
+
+
+def test_host_side_validation_of_the_dot_entry_point(lib):
+    """Every rejection happens before any launch (no GPU needed).  `p`: a non-null, 16-byte aligned dummy, validated, never
+    dereferenced on the host."""
+    p = 64
+
+    def status(U=p, ldu=64, I=p, ldi=64, d=64, u=p, nq=5, ni=100, topn=10, nsplit=0, top=p, ws=p, fo=None, fi=None):
+        with pytest.raises(lib.KtupError) as e:
+            lib.call('ktup_eval_dot_topk', U, ldu, I, ldi, d, u, nq, ni, None, None, fo, fi, topn, nsplit, top, None, ws, None)
+        assert 'ktup_eval_dot_topk' in str(e.value)
+        return e.value.code
+
+    assert status(U=None) == ERR_INVALID
+    assert status(topn=0) == ERR_INVALID
+    assert status(nq=-1) == ERR_INVALID
+    assert status(d=0) == ERR_INVALID
+    assert status(ni=0) == ERR_INVALID
+    assert status(ldu=63) == ERR_INVALID                    # a pitch below the width
+    assert status(nsplit=-2) == ERR_INVALID
+    assert status(top=None) == ERR_INVALID
+    assert status(ws=None) == ERR_INVALID
+    assert status(fo=p) == ERR_INVALID                      # filter offsets without ids
+    assert status(topn=17) == ERR_UNSUPPORTED
+    assert status(d=257, ldu=257, ldi=257) == ERR_UNSUPPORTED
+    assert status(ni=2 ** 31) == ERR_UNSUPPORTED
+    assert lib.ERR_UNSUPPORTED == ERR_UNSUPPORTED
+
+
+def test_wrapper_rejects_cpu_tensors(lib):
+    import torch
+    from jTransUP.hip import ops
+    U, I = torch.zeros(9, 8), torch.zeros(7, 8)
+    with pytest.raises(lib.KtupError):
+        ops.eval_dot_topk(U, I, torch.zeros(4, dtype=torch.int64), 10)

@@ -1,0 +1,339 @@
+"""The one-sweep evaluation pass of the inner-product recommenders (ktup_eval_dot_topk; BPRMF, FM, CKE, coFM) on the GPU:
+bit-identity with the matrix route (K11 + the two torch adds + the ranking kernel), exact ties, the reference's own evaluation
+matrices, the models through the driver (eager and as a replayed graph) and the command lines with the pass on and off."""
+import os
+import re
+import subprocess
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from tests.synth import make_dataset
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, 'joint-kg-recommender_amd')
+
+
+def ops():
+    from jTransUP.hip import ops as o
+    return o
+
+
+def matrix_route(U, I, u, topn, f_off, f_ids, ua, ia):
+    """What the batch walk computes: K11 per 512 users, the two adds in evaluate()'s order, the filtered descending top-n."""
+    ids, scs = [], []
+    nq = u.numel()
+    for s in range(0, nq, 512):
+        e = min(nq, s + 512)
+        mat = ops().eval_bprmf(U, I, u[s:e])
+        if ua is not None:
+            mat = mat + ua[s:e][:, None]
+        if ia is not None:
+            mat = mat + ia[None, :]
+        fo = fi = None
+        if f_off is not None:
+            lo = int(f_off[s])
+            fo, fi = (f_off[s:e + 1] - lo).contiguous(), f_ids[lo:]
+        t, sc = ops().topk_filtered(mat, True, topn, fo, fi, with_scores=True)
+        ids.append(t); scs.append(sc)
+    return torch.cat(ids), torch.cat(scs)
+
+
+def filters(rng, nq, ni, mean):
+    """CSR filter lists per query: random sizes around `mean`, query 1 filtered completely, query 2 with an empty list."""
+    sizes = rng.randint(0, 2 * mean + 1, size=nq)
+    if nq > 1:
+        sizes[1] = ni
+    if nq > 2:
+        sizes[2] = 0
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    flat = rng.randint(0, ni, size=int(off[-1])).astype(np.int32)         # (repeated ids inside a list are harmless to both routes)
+    if nq > 1:
+        flat[off[1]:off[2]] = np.arange(ni, dtype=np.int32)
+    return torch.from_numpy(off).to(DEV), torch.from_numpy(flat).to(DEV)
+
+
+SHAPES = [(64, 300, 177, 65, 16), (100, 70, 5, 63, 10), (37, 90, 33, 1, 3), (50, 500, 1000, 129, 1), (20, 64, 45, 33, 10),
+          (256, 40, 130, 17, 10), (8, 50, 40000, 33, 10), (64, 6040, 3240, 6040, 10)]
+_CASES = {}
+
+
+def case(shape):
+    """Inputs of a shape and the matrix route's lists for its four variants, made once and left unchanged."""
+    if shape in _CASES:
+        return _CASES[shape]
+    d, nu, ni, nq, topn = shape
+    gen = torch.Generator().manual_seed(d * 7 + ni)
+    rng = np.random.RandomState(ni + nq)
+    U = (torch.randn(nu, d, generator=gen) * 0.5).to(DEV)
+    I = (torch.randn(ni, d, generator=gen) * 0.5).to(DEV)
+    u = torch.randint(0, nu, (nq,), generator=gen)
+    if nq > 4:
+        u[4] = u[0]; u[nq - 1] = u[3]                                     # duplicates
+    u = u.to(DEV)
+    scale = 0.25 * d ** 0.5                                               # the spread of the dot products: the terms reorder the lists
+    ua = (torch.randn(nq, generator=gen) * scale).to(DEV)
+    ia = (torch.randn(ni, generator=gen) * scale).to(DEV)
+    f_off, f_ids = filters(rng, nq, ni, min(165, max(2, ni // 8)))
+    want = {}
+    for terms in (False, True):
+        for filt in (False, True):
+            want[terms, filt] = matrix_route(U, I, u, topn, f_off if filt else None, f_ids if filt else None,
+                                             ua if terms else None, ia if terms else None)
+    if topn > 1 and ni > topn:
+        assert not torch.equal(want[False, False][0], want[True, False][0])   # the item terms do reorder
+    _CASES[shape] = (U, I, u, ua, ia, f_off, f_ids, want)
+    return _CASES[shape]
+
+
+@pytest.mark.parametrize('filt', [True, False])
+@pytest.mark.parametrize('terms', [False, True])
+@pytest.mark.parametrize('shape', SHAPES)
+def test_pass_is_the_matrix_route_bit_for_bit(shape, terms, filt):
+    d, nu, ni, nq, topn = shape
+    U, I, u, ua, ia, f_off, f_ids, want = case(shape)
+    got = ops().eval_dot_topk(U, I, u, topn, f_off if filt else None, f_ids if filt else None, ua if terms else None,
+                              ia if terms else None, with_scores=True)
+    w_ids, w_sc = want[terms, filt]
+    assert got[0].dtype == torch.int32 and tuple(got[0].shape) == (nq, topn)
+    assert torch.equal(got[0], w_ids)
+    assert torch.equal(got[1], w_sc)
+    if filt and nq > 2:
+        assert bool((got[0][1] == -1).all())                              # query 1: everything filtered
+    if ni < topn:
+        assert bool((got[0][:, ni:] == -1).all())
+    only = ops().eval_dot_topk(U, I, u, topn, f_off if filt else None, f_ids if filt else None, ua if terms else None,
+                               ia if terms else None)
+    assert torch.equal(only, w_ids)                                       # top_scores == NULL
+
+
+@pytest.mark.parametrize('nsplit', [0, 1, 3, 8])
+@pytest.mark.parametrize('shape', [SHAPES[0], SHAPES[6]])
+def test_any_number_of_catalogue_splits(shape, nsplit):
+    U, I, u, ua, ia, f_off, f_ids, want = case(shape)
+    got = ops().eval_dot_topk(U, I, u, shape[4], f_off, f_ids, ua, ia, with_scores=True, nsplit=nsplit)
+    assert torch.equal(got[0], want[True, True][0]) and torch.equal(got[1], want[True, True][1])
+
+
+def test_user_table_with_a_pitch_and_unaligned_item_rows():
+    """A column slice as the user table (pitch > d) and an item table whose rows start off a 16-byte boundary."""
+    d, nu, ni, nq, topn = SHAPES[4]
+    U, I, u, ua, ia, f_off, f_ids, want = case(SHAPES[4])
+    wide = torch.zeros(nu, d + 12, device=DEV)
+    wide[:, 5:5 + d] = U
+    wide_i = torch.zeros(ni, d + 3, device=DEV)
+    wide_i[:, 1:1 + d] = I
+    got = ops().eval_dot_topk(wide[:, 5:5 + d], wide_i[:, 1:1 + d], u, topn, f_off, f_ids, ua, ia, with_scores=True)
+    assert torch.equal(got[0], want[True, True][0]) and torch.equal(got[1], want[True, True][1])
+
+
+@pytest.mark.parametrize('nsplit', [0, 1, 4, 8])
+def test_exact_ties_go_to_the_lower_id(nsplit):
+    """7 distinct item rows repeated at random and an item term with ties of its own: many exactly equal scores inside a tile,
+    across tiles and across splits; the lists are the matrix route's."""
+    d, nu, ni, nq, topn = 64, 40, 200, 40, 16
+    gen = torch.Generator().manual_seed(11)
+    rng = np.random.RandomState(11)
+    U = (torch.randn(nu, d, generator=gen) * 0.5).to(DEV)
+    rows = torch.randn(7, d, generator=gen) * 0.5
+    I = rows[torch.randint(0, 7, (ni,), generator=gen)].contiguous().to(DEV)
+    ia = torch.tensor([0.0, 0.5, -0.25])[torch.randint(0, 3, (ni,), generator=gen)].to(DEV)
+    u = torch.randint(0, nu, (nq,), generator=gen).to(DEV)
+    f_off, f_ids = filters(rng, nq, ni, 20)
+    for terms in (None, ia):
+        w_ids, w_sc = matrix_route(U, I, u, topn, f_off, f_ids, None, terms)
+        assert int((w_sc[0][1:] == w_sc[0][:-1]).sum()) > 0               # ties among the best of a row
+        got = ops().eval_dot_topk(U, I, u, topn, f_off, f_ids, None, terms, with_scores=True, nsplit=nsplit)
+        assert torch.equal(got[0], w_ids) and torch.equal(got[1], w_sc)
+
+
+def test_declined_shapes_return_none():
+    U, I, u = case(SHAPES[4])[:3]
+    assert ops().eval_dot_topk(U, I, u, 17) is None
+    assert ops().eval_dot_topk(U, I, u[:0], 10) is None
+    wide = torch.zeros(8, 260, device=DEV)
+    assert ops().eval_dot_topk(wide, wide, u[:3] % 8, 10) is None
+
+
+# ------------------------------------------------------------------------------------------ the reference's own matrices
+NU, NI, NE, NR = 37, 45, 53, 7
+
+
+def _load(model, g, prefix):
+    model.load_state_dict({k: torch.from_numpy(g[prefix + k]).to(DEV) for k in model.state_dict()})
+
+
+def _golden_model(golden, name, d):
+    from jTransUP.models import CKE, bprmf, cofm, fm
+    if name == 'bprmf':
+        g = golden('eval_small')
+        m = bprmf.BPRMF(20, NU, NI)
+        _load(m, g, 'bprmf.')
+        return m, g['uq'], g['bprmf.eval']
+    p = 'd%d.' % d
+    if name == 'fm':
+        g = golden('fm_cofm')
+        m = fm.FM(d, NU, NI)
+        _load(m, g, p + 'fm.')
+        return m, g[p + 'uq'], g[p + 'fm.eval']
+    if name == 'cofm':
+        g = golden('fm_cofm')
+        m = cofm.coFM(False, d, NU, NI, NE, NR, False)
+        _load(m, g, p + 'cofm.own.')
+        return m, g[p + 'uq'], g[p + 'cofm.own.L2.evalRec']
+    g = golden('baselines')
+    i2e = g[p + 'cke.item2ent']
+    m = CKE.CKE(False, d, NU, NI, NE, NR, {i: i for i in range(NI)}, {i: ((int(i2e[i]) if i2e[i] != NE else -1), i) for i in range(NI)})
+    _load(m, g, p + 'cke.')
+    return m, g[p + 'uq'], g[p + 'cke.L2.evalRec']
+
+
+def _dot_args(m):
+    """(U, I, user_add, item_add) of a model's pass, for a given id tensor."""
+    with torch.no_grad():
+        I = m._item_side().contiguous() if hasattr(m, '_item_side') else m.item_embeddings.weight
+        if hasattr(m, 'user_bias'):
+            return m.user_embeddings.weight, I, (lambda u: m.bias + m.user_bias(u)), m.item_bias.weight
+        return m.user_embeddings.weight, I, (lambda u: None), None
+
+
+@pytest.mark.parametrize('name,d', [('bprmf', 20), ('fm', 36), ('fm', 64), ('cofm', 36), ('cofm', 64), ('cke', 36), ('cke', 64)])
+def test_reference_goldens(golden, name, d):
+    """The top-10 ids of the pass are those of a stable sort by (-score, id) of the reference's own eval / evalRec matrix.
+    Precondition, asserted first: the smallest gap between consecutive scores among each golden row's best 11 exceeds 8 x the
+    largest |pass score - golden score| of the case (so rounding cannot have swapped two neighbours)."""
+    m, uq, ref = _golden_model(golden, name, d)
+    m.eval()
+    u = torch.from_numpy(uq).long().to(DEV)
+    order = np.argsort(-ref, axis=1, kind='stable')
+    best = np.take_along_axis(ref, order[:, :11], axis=1).astype(np.float64)
+    gap = float((best[:, :-1] - best[:, 1:]).min())
+    U, I, ua, ia = _dot_args(m)
+    with torch.no_grad():
+        ids, sc = ops().eval_dot_topk(U, I, u, 10, None, None, ua(u), ia, with_scores=True)
+    ids_h, sc_h = ids.cpu().numpy(), sc.cpu().numpy()
+    assert (ids_h >= 0).all()
+    err = float(np.abs(sc_h.astype(np.float64) - np.take_along_axis(ref, ids_h.astype(np.int64), axis=1)).max())
+    print('%s d=%d: smallest gap %.3g, largest score error %.3g' % (name, d, gap, err))
+    assert gap > 8 * err
+    np.testing.assert_array_equal(ids_h, order[:, :10])
+    assert torch.equal(m.evaluate_topk(u, None, 10), ids)                 # the model's own entry: the same call
+
+
+# ------------------------------------------------------------------------------------------ models and driver
+def _world_model(name):
+    from jTransUP.models import CKE, bprmf, cofm, fm
+    torch.manual_seed(13)
+    nu, ni, ne, nr, d = 90, 230, 230, 6, 36
+    if name == 'bprmf':
+        m = bprmf.BPRMF(d, nu, ni)
+    elif name == 'fm':
+        m = fm.FM(d, nu, ni)
+    elif name == 'cke':
+        m = CKE.CKE(False, d, nu, ni, ne, nr, {i: i for i in range(ni)}, {i: ((i * 3) % ne if i % 5 else -1, i) for i in range(ni)})
+    else:
+        m = cofm.coFM(False, d, nu, ni, ne, nr, name == 'cofm_share')
+    with torch.no_grad():
+        for p in m.parameters():                                          # (the bias tables start at zero)
+            p.add_(torch.randn_like(p) * 0.3)
+    m.eval(); m.disable_grad()
+    return m, nu, ni
+
+
+def _world_pass(m, nu, ni, seed=4):
+    rng = np.random.RandomState(seed)
+    users = list(range(nu))
+    gold = {u: set(rng.choice(ni, size=rng.randint(1, 9), replace=False).tolist()) for u in users if u % 9}
+    train = {u: set(rng.choice(ni, size=25, replace=False).tolist()) for u in users}
+    batches = [users[s:s + 32] for s in range(0, nu, 32)]
+    score_fn = m.evaluate if hasattr(m, 'evaluate') else (lambda u: m.evaluateRec(u))
+    pass_fn = lambda u, fo, fi, n: m.evaluate_topk(u, None, n, fo, fi)
+    return gold, train, batches, score_fn, pass_fn
+
+
+@pytest.mark.parametrize('name', ['bprmf', 'fm', 'cke', 'cofm', 'cofm_share'])
+def test_driver_pass_equals_the_batch_walk(name, monkeypatch):
+    from jTransUP.models import _driver as D
+    m, nu, ni = _world_model(name)
+    gold, train, batches, score_fn, pass_fn = _world_pass(m, nu, ni)
+    calls = []
+
+    def counted(u, fo, fi, n):
+        out = pass_fn(u, fo, fi, n)
+        calls.append(out is not None)
+        return out
+    for topn in (10, 17):
+        FL = types.SimpleNamespace(topn=topn)
+        walk = D.rec_eval_pass(FL, score_fn, batches, gold, [train], True, want_rows=False)
+        fused = D.rec_eval_pass(FL, score_fn, batches, gold, [train], True, want_rows=False, pass_fn=counted, pass_descending=True)
+        assert walk.shape == (sum(1 for u in range(nu) if u % 9), 5)
+        np.testing.assert_array_equal(fused, walk)
+        assert calls[-1] == (topn == 10 and name != 'cofm_share')         # shared tables and topn 17 fall back to the walk
+    n = len(calls)
+    FL = types.SimpleNamespace(topn=10)
+    D.rec_eval_pass(FL, score_fn, batches, gold, [train], True, want_rows=False, pass_fn=counted)             # the default: ascending passes only
+    D.rec_eval_pass(FL, score_fn, batches, gold, [train], False, want_rows=False, pass_fn=counted, pass_descending=True)
+    monkeypatch.setenv('KTUP_EVAL_PASS', '0')
+    D.rec_eval_pass(FL, score_fn, batches, gold, [train], True, want_rows=False, pass_fn=counted, pass_descending=True)
+    assert len(calls) == n
+
+
+@pytest.mark.parametrize('name', ['fm', 'cke'])
+def test_pass_replayed_as_a_graph_follows_the_tables(name):
+    """_driver._rec_eval_fused with model_graph_key: eager, captured, replayed -- every pass sees the tables as they are now
+    (FM: the bias terms are formed inside the pass; CKE: so is the item side)."""
+    from jTransUP.models import _driver as D
+    m, nu, ni = _world_model(name)
+    gold, train, batches, score_fn, pass_fn = _world_pass(m, nu, ni, seed=6)
+    index = D.rank_index(batches, gold, [train])
+    FL = types.SimpleNamespace(topn=10)
+    for step in range(3):
+        key = D.model_graph_key(m)
+        got = D._rec_eval_fused(FL, pass_fn, batches, index, key)
+        want = D._rec_eval_fused(FL, pass_fn, batches, index, None)
+        np.testing.assert_array_equal(got, want)
+        walk = D.rec_eval_pass(FL, score_fn, batches, gold, [train], True, want_rows=False)
+        np.testing.assert_array_equal(got, walk)
+        entry = D._EVAL_GRAPHS[(id(batches), id(index), 10, key)]
+        assert (entry[0] is None) == (step == 0)                          # eager once, then a graph
+        with torch.no_grad():                                              # a training step's worth of change, in place
+            for p in m.parameters():
+                p.add_(torch.randn_like(p) * 0.05)
+
+
+# ------------------------------------------------------------------------------------------ command lines
+@pytest.fixture(scope='module')
+def dataset(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp('ds')
+    make_dataset(str(tmp))
+    return tmp
+
+
+def _eval_lines(script, data, name, extra, env):
+    logs = os.path.join(data, 'log')
+    os.makedirs(logs, exist_ok=True)
+    cmd = [sys.executable, os.path.join(PKG, script), '-data_path', data, '-log_path', logs, '-dataset', 'ml1m', '-experiment_name', name,
+           '-nohas_visualization', '-batch_size', '32', '-embedding_size', '36', '-seed', '3', '-eval_interval_steps', '6',
+           '-training_steps', '12', '-early_stopping_steps_to_wait', '0', '-learning_rate', '0.05', '-topn', '10'] + extra
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    log = open(os.path.join(logs, name + '.log')).read()
+    return re.findall(r'f1:\d\.\d+, p:\d\.\d+, r:\d\.\d+, hit:\d\.\d+, ndcg:\d\.\d+, topn:10', log)
+
+
+@pytest.mark.parametrize('script,model,extra', [
+    ('run_item_recommendation.py', 'bprmf', []), ('run_item_recommendation.py', 'fm', []),
+    ('run_knowledgable_recommendation.py', 'cke', ['-kg_test_files', 'valid.dat', '-joint_ratio', '0.5']),
+    ('run_knowledgable_recommendation.py', 'cofm', ['-kg_test_files', 'valid.dat', '-joint_ratio', '0.5'])])
+def test_command_lines_log_the_same_metrics_with_the_pass_on_and_off(dataset, script, model, extra):
+    args = ['-model_type', model, '-rec_test_files', 'valid.dat'] + extra
+    env = {k: v for k, v in os.environ.items() if k != 'KTUP_EVAL_PASS'}
+    on = _eval_lines(script, str(dataset), 'dot-' + model + '-on', args, env)
+    off = _eval_lines(script, str(dataset), 'dot-' + model + '-off', args, dict(env, KTUP_EVAL_PASS='0'))
+    assert len(on) >= 2
+    assert on == off
