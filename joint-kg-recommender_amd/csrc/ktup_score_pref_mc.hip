@@ -13,8 +13,10 @@
 // kernel's time is (MFMA passes + VALU instructions + exposed memory).  pref_fwd4 spends ~4000 clk per tile in MFMA
 // and ~3500 clk in address arithmetic, bounds checks and scalar float4 math, because its geometry is run-time data.
 // Here everything about the geometry is a template constant:
-//   * gather: (row, chunk) of each of a lane's J loads is loop invariant; one v_mad_u64_u32 + one v_lshl_add_u64 per
-//     row load (ids read from LDS with immediate offsets);
+//   * gather: (row, chunk) of each of a lane's J loads is loop invariant and the ids are read from LDS with immediate offsets.
+//     Through 64-bit pointers a load group (one row of each of the three tables) still compiles to 11 instructions on 64-bit
+//     pairs (three v_mad_u64_u32, six v_lshl_add_u64, a shift, moves: the fences that keep the kernel inside 128 VGPRs also keep
+//     the chunk offset from folding); with BUF (below) it is one v_add_u32 per load;
 //   * all LDS operand addresses are one base register + immediates; no bounds checks in the matrix phases;
 //   * x / q / distance math on <4 x float> values -> v_pk_add_f32 / v_pk_fma_f32;
 //   * when the last 16-slot preference tile holds <= 4 preferences (P = 20), its logits come from
@@ -41,6 +43,7 @@
 
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 
 #include "ktup_common.h"
 #include "ktup_pref_geom.h"
@@ -127,8 +130,17 @@ struct McArgs {
 
 // L1: the distance is compile-time too -- with a run-time flag the compiler evaluates |z| AND z^2 for every coordinate and
 // selects (v_and + v_cndmask per element: ~70 of a tile's ~330 VALU instructions).
-template <typename G, bool L1>
+//
+// BUF (option fwd_buf_gather, soft gate, d <= 128): the 16 lanes that load a tile's ids also form each row's BYTE offset id * pitch, once,
+// and the sid slots hold its low 32 bits instead of the id; the row loads are buffer loads (one descriptor per table in scalar
+// registers: base = the table, 2^32 - 1 records) whose 32-bit lane offset is ONE v_add_u32 of the row's offset and the lane's
+// loop-invariant chunk offset -- with 64-bit pointers every lane rebuilt id * pitch + chunk for every load (11 instructions on 64-bit
+// pairs per load group of three tables).  The library's ABI carries no row counts, so the kernel decides per tile: a tile is FAST when
+// every one of its 48 rows ends at or below byte 2^32 - 1 of its table (one ballot of the id lanes; the flag travels with the
+// prefetched offsets); any other tile re-reads its ids and gathers through 64-bit pointers as the !BUF kernel does.
+template <typename G, bool L1, bool BUF = false>
 __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
+  static_assert(!BUF || (!G::HARD && G::NCH <= 32), "the buffer-load gather is the soft gate's, d <= 128");
   KTUP_RESOLVE_GUMBEL(a);
   constexpr int NCH = G::NCH, NP = G::NP, KG = G::KG, CT = G::CT, PTF = G::PTF, J = G::J, TOTAL = G::TOTAL;
   constexpr int PITCHA4 = G::PITCHA4, TPITCH = G::TPITCH, KQ = G::KQ;
@@ -216,6 +228,19 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
     gc[jj] = past ? 0 : e % NCH;
   }
   const bool last_ok = lane + 64 * (J - 1) < TOTAL;
+  // BUF: the descriptors, the lane's chunk byte offsets, and what turns an id into its row's offset.  id * pitch in float4 units is exact
+  // in 64 bits (two 32-bit factors); the row [16 o, 16 o + 16 NCH) ends at or below byte 2^32 - 1 iff o <= 2^28 - 1 - NCH.
+  [[maybe_unused]] __amdgpu_buffer_rsrc_t rsU, rsI, rsE;
+  [[maybe_unused]] uint32_t gcb[J];
+  if constexpr (BUF) {
+    rsU = __builtin_amdgcn_make_buffer_rsrc(const_cast<v4*>(a.U), 0, (int)0xffffffffu, 0x00020000);
+    rsI = __builtin_amdgcn_make_buffer_rsrc(const_cast<v4*>(a.I), 0, (int)0xffffffffu, 0x00020000);
+    rsE = __builtin_amdgcn_make_buffer_rsrc(const_cast<v4*>(HASE ? a.E : a.U), 0, (int)0xffffffffu, 0x00020000);
+#pragma unroll
+    for (int jj = 0; jj < J; ++jj) gcb[jj] = 16u * (uint32_t)gc[jj];
+  }
+  constexpr uint64_t OMAX = (1ull << 28) - 1 - NCH;
+  bool fast = true;                                              // BUF: this tile's rows are all in reach of 32-bit offsets (wave-uniform)
   const v4* xb = xt + j * NCH + kq;                              // stage-1 B operand / q rows of this lane
   const v4* tab = AlogS + j * PITCHA4 + kq;                      // stage-1 A operand
   const float* tn0 = CnS + kq * TPITCH + j;
@@ -234,13 +259,26 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
     // SPLIT: the id loads index with a per-tile opaque copy of the lane number -- hoisted out of the tile loop, the 64-bit byte offset
     // of the lane is the register pair that tips this kernel over 128 (it was spilled, and reloaded in front of every id load)
     int idl = lane;
-    if constexpr (SPLIT) asm volatile("" : "+v"(idl));
+    if constexpr (SPLIT || BUF) asm volatile("" : "+v"(idl));
+    bool far = false;
     if (first && lane < 16) {
       const bool ok = lane < rem;
       const int64_t uid = ok ? (a.u_ids + row0)[idl] : 0, iid = ok ? (a.i_ids + row0)[idl] : 0;
-      sid[lane] = (int32_t)uid;
-      sid[16 + lane] = (int32_t)iid;
-      sid[32 + lane] = HASE ? a.item2ent[iid] : 0;
+      if constexpr (BUF) {
+        const uint64_t ou = (uint64_t)(uint32_t)uid * a.ldu4, oi = (uint64_t)(uint32_t)iid * a.ldi4;
+        const uint64_t oe = HASE ? (uint64_t)(uint32_t)a.item2ent[iid] * a.lde4 : 0;
+        far = ou > OMAX || oi > OMAX || oe > OMAX;
+        sid[lane] = (int32_t)((uint32_t)ou << 4);
+        sid[16 + lane] = (int32_t)((uint32_t)oi << 4);
+        sid[32 + lane] = (int32_t)((uint32_t)oe << 4);
+      } else {
+        sid[lane] = (int32_t)uid;
+        sid[16 + lane] = (int32_t)iid;
+        sid[32 + lane] = HASE ? a.item2ent[iid] : 0;
+      }
+    }
+    if constexpr (BUF) {
+      if (first) fast = __builtin_amdgcn_ballot_w64(far) == 0;
     }
     first = false;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -249,6 +287,57 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
     // already several times the latency-bandwidth product, and 3 x J live float4 would push the kernel past 128 VGPRs.
     v4 q[J];
     constexpr int JA = G::NW >= 16 ? (J + 1) / 2 : J;
+    if constexpr (BUF) {
+      auto gather = [&](auto by_offset) {                        // by_offset: buffer loads at the 32-bit offsets in the sid slots
+        constexpr bool OFFS = decltype(by_offset)::value;
+#pragma unroll
+        for (int j0 = 0; j0 < J; j0 += JA) {
+          v4 uu[JA], vv[JA], ee[JA];
+#pragma unroll
+          for (int jb = 0; jb < JA; ++jb) {
+            const int jj = j0 + jb;
+            if (jj < J) {
+              if constexpr (OFFS) {
+                uu[jb] = __builtin_bit_cast(v4, __builtin_amdgcn_raw_buffer_load_b128(rsU, (int)((uint32_t)sid[grow[jj]] + gcb[jj]), 0, 0));
+                vv[jb] = __builtin_bit_cast(v4, __builtin_amdgcn_raw_buffer_load_b128(rsI, (int)((uint32_t)sid[16 + grow[jj]] + gcb[jj]), 0, 0));
+                if (HASE) ee[jb] = __builtin_bit_cast(v4, __builtin_amdgcn_raw_buffer_load_b128(rsE, (int)((uint32_t)sid[32 + grow[jj]] + gcb[jj]), 0, 0));
+              } else {
+                uint32_t gs = gcb[jj];
+                asm volatile("" : "+v"(gs));   // opaque, as gc[jj] in the pointer kernel: nothing of this cold branch is worth a register outside it
+                uu[jb] = a.U[(uint64_t)(uint32_t)sid[grow[jj]] * a.ldu4 + (gs >> 4)];
+                vv[jb] = a.I[(uint64_t)(uint32_t)sid[16 + grow[jj]] * a.ldi4 + (gs >> 4)];
+                if (HASE) ee[jb] = a.E[(uint64_t)(uint32_t)sid[32 + grow[jj]] * a.lde4 + (gs >> 4)];
+              }
+            }
+          }
+#pragma unroll
+          for (int jb = 0; jb < JA; ++jb) {
+            const int jj = j0 + jb;
+            if (jj < J) {
+              const v4 ve = HASE ? vv[jb] + ee[jb] : vv[jb];
+              if (jj < J - 1 || last_ok) xt[lane + 64 * jj] = uu[jb] + ve;
+              q[jj] = uu[jb] + (-ve);
+            }
+          }
+        }
+      };
+      if (__builtin_expect(fast, 1)) {
+        gather(std::true_type{});
+      } else {
+        // cold: a row of this tile lies (partly) past byte 2^32 - 1 of its table.  Its ids once more, into the sid slots in place of
+        // the offsets, and the gather through 64-bit pointers
+        if (lane < 16) {
+          const bool ok = lane < rem;
+          const int64_t uid = ok ? (a.u_ids + row0)[idl] : 0, iid = ok ? (a.i_ids + row0)[idl] : 0;
+          sid[lane] = (int32_t)uid;
+          sid[16 + lane] = (int32_t)iid;
+          sid[32 + lane] = HASE ? a.item2ent[iid] : 0;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        gather(std::false_type{});
+      }
+    } else {
 #pragma unroll
     for (int j0 = 0; j0 < J; j0 += JA) {
       v4 uu[JA], vv[JA], ee[JA];
@@ -281,17 +370,26 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
         }
       }
     }
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // ---- next tile's ids travel under the matrix phases
     int32_t nx_u = 0, nx_i = 0, nx_e = 0;
+    bool nx_far = false;
     const bool pre = lane < 16 && tile_id + wstride < ntiles;
     if (pre) {
       const int64_t row1 = (tile_id + wstride) * 16;
       const bool ok = lane < a.n - row1;
       const int64_t uid = ok ? (a.u_ids + row1)[idl] : 0, iid = ok ? (a.i_ids + row1)[idl] : 0;
-      nx_u = (int32_t)uid; nx_i = (int32_t)iid;
-      nx_e = HASE ? a.item2ent[iid] : 0;
+      if constexpr (BUF) {
+        const uint64_t ou = (uint64_t)(uint32_t)uid * a.ldu4, oi = (uint64_t)(uint32_t)iid * a.ldi4;
+        const uint64_t oe = HASE ? (uint64_t)(uint32_t)a.item2ent[iid] * a.lde4 : 0;
+        nx_far = ou > OMAX || oi > OMAX || oe > OMAX;
+        nx_u = (int32_t)((uint32_t)ou << 4); nx_i = (int32_t)((uint32_t)oi << 4); nx_e = (int32_t)((uint32_t)oe << 4);
+      } else {
+        nx_u = (int32_t)uid; nx_i = (int32_t)iid;
+        nx_e = HASE ? a.item2ent[iid] : 0;
+      }
     }
     // ---- stage 1: logits^T.  lg[tt][reg] of lane (kq, pair j) = logit of preference 16 tt + 4 reg + kq
     v4 lg[G::PT];
@@ -518,6 +616,7 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
     const float score = allsum_kq((dacc[0] + dacc[1]) + (dacc[2] + dacc[3]));
     if (kq == 0 && j < rem) (a.score + row0)[j] = score;
     if (pre) { sid[lane] = nx_u; sid[16 + lane] = nx_i; sid[32 + lane] = nx_e; }
+    if constexpr (BUF) fast = __builtin_amdgcn_ballot_w64(nx_far) == 0;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
@@ -772,18 +871,18 @@ int launch_fwd_wide(const McArgs& a, int np, hipStream_t st, const char* name) {
 #undef KTUP_FW
 }
 
-template <typename G, bool L1>
+template <typename G, bool L1, bool BUF = false>
 int launch_mc_l(const McArgs& a, hipStream_t st, const char* name) {
   static_assert(G::NW >= 2, "LDS budget");
   constexpr size_t lds = G::TABLE_BYTES + (size_t)G::NW * G::WAVE_BYTES;
-  (void)hipFuncSetAttribute((const void*)pref_fwd_mc_kernel<G, L1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute((const void*)pref_fwd_mc_kernel<G, L1, BUF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int64_t ntiles = (a.n + 15) / 16;
   // small batches (a B = 512 training step is 64 tiles): fewer waves per workgroup, so that the tiles spread over many CUs
   // (one tile per SIMD) instead of queueing four deep on the matrix pipe of four CUs
   int nw = (int)((ntiles + 255) / 256);
   nw = nw < 4 ? (G::NW < 4 ? G::NW : 4) : (nw > G::NW ? G::NW : nw);
   const int grid = grid_for((ntiles + nw - 1) / nw, 256);
-  hipLaunchKernelGGL((pref_fwd_mc_kernel<G, L1>), dim3(grid), dim3(nw * 64), lds, st, a);
+  hipLaunchKernelGGL((pref_fwd_mc_kernel<G, L1, BUF>), dim3(grid), dim3(nw * 64), lds, st, a);
   return check_launch(name);
 }
 
@@ -792,6 +891,11 @@ int launch_mc(const McArgs& a, hipStream_t st, const char* name) {
   if constexpr (G::NW < 2) {
     return 1;                                   // tables + one wave's tiles exceed the LDS: the caller's generic kernel runs
   } else {
+    // option fwd_buf_gather: rows through buffer loads at 32-bit offsets (soft gate, d <= 128; the nontemporal hint is a compile-time
+    // bit of a buffer load, and the tables it is for are the > 4 GB ones: nt_gather keeps the pointer kernel)
+    if constexpr (!G::HARD && G::NCH <= 32) {
+      if (opt_fwd_buf_gather() && !a.nt) return a.l1 ? launch_mc_l<G, true, true>(a, st, name) : launch_mc_l<G, false, true>(a, st, name);
+    }
     return a.l1 ? launch_mc_l<G, true>(a, st, name) : launch_mc_l<G, false>(a, st, name);
   }
 }
