@@ -23,7 +23,7 @@ PER_FILE_FLAGS = {'ktup_score_pref.hip': ['-fno-slp-vectorize'], 'ktup_eval.hip'
                   'ktup_transd_eval.hip': ['-fno-slp-vectorize']}
 # Extension directories under csrc/, each with its own C header under include/: compiled into the same library (objects are
 # prefixed with the directory's name).  csrc/*.hip itself stays the set of translation units the committed profiles were taken from.
-EXTENSIONS = {'transd': 'ktup_transd.h', 'dot': 'ktup_dot.h'}
+EXTENSIONS = {'transd': 'ktup_transd.h', 'dot': 'ktup_dot.h', 'dotstep': 'ktup_dot_step.h'}
 
 
 def _sources():

@@ -182,6 +182,13 @@ SIGNATURES_DOT = {
 }
 _RESTYPE.update({'ktup_eval_dot_topk_workspace_bytes': ctypes.c_size_t})
 
+# The training step of the inner-product recommenders (include/ktup_dot_step.h; kernels under csrc/dotstep/, same library).
+SIGNATURES_DOT_STEP = {
+    'ktup_train_dot_step_supported': [c_i],
+    'ktup_train_dot_step': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_i, c_p, c_p, c_l, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p],
+    'ktup_reg_align_pairs': [c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_l, c_i, c_f, c_p, c_p, c_p, c_p],
+}
+
 _lib = None
 
 
@@ -201,7 +208,8 @@ def load():
         raise KtupError('libktup_hip.so not found at %s -- build it with '
                         '`python joint-kg-recommender_amd/build_hip.py` (there is no CPU fallback)' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_TRANSD.items()) + list(SIGNATURES_DOT.items()):
+    for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_TRANSD.items()) + list(SIGNATURES_DOT.items()) \
+            + list(SIGNATURES_DOT_STEP.items()):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, ctypes.c_int)

@@ -48,12 +48,25 @@ def evaluate(FLAGS, model, eval_iter, eval_dict, all_dicts, logger, eval_descend
     return perf
 
 
+def _stepper_class(FLAGS):
+    """The GPU-resident stepper of this model and width, or None (the autograd route)."""
+    if FLAGS.model_type in ('transup', 'bprmf'):
+        # TUP / BPRMF: utils/fast_train.py RecStepper (a TUP width that is not a multiple of 4: the autograd route)
+        from jTransUP.utils.fast_train import RecStepper
+        return RecStepper if FLAGS.model_type == 'bprmf' or FLAGS.embedding_size % 4 == 0 else None
+    if FLAGS.model_type == 'fm':
+        # FM: the whole rec step is ktup_train_dot_step (utils/fast_train_dot.py), fed like TUP's fused step under -device_sampling
+        from jTransUP.utils.fast_train_dot import DotRecStepper, dot_step_supported
+        return DotRecStepper if dot_step_supported(FLAGS.embedding_size) else None
+    return None
+
+
 def train_loop(FLAGS, model, trainer, train_dataset, eval_datasets, user_total, item_total, logger, vis=None, is_report=False):
     train_iter, train_total, train_list, train_dict = train_dataset
     all_dicts = [train_dict] + [d[3] for d in eval_datasets] if FLAGS.filter_wrong_corrupted else None
     # TUP / BPRMF: the step body below as a handful of C-ABI launches (utils/fast_train.py RecStepper), optionally with the
     # training data and the negative sampling on the device (-device_sampling)
-    stepper = feed = sampler = None
+    stepper = feed = sampler = stepper_class = None
     sharded = bool(getattr(FLAGS, 'shard_tables', False))
     if sharded:
         # config 3 at scale: TUP's user / item tables row-sharded over the ranks, fixed-shape exchange, row-sparse optimizer on the touched
@@ -69,11 +82,11 @@ def train_loop(FLAGS, model, trainer, train_dataset, eval_datasets, user_total, 
             sampler.set_rating_dicts(user_total, item_total, all_dicts)
             feed = DeviceFeeder(train_list, FLAGS.batch_size, D.DEV, FLAGS.negtive_samples, seed=FLAGS.seed)
             logger.info('Training data and negative sampling are device-resident (-device_sampling).')
-    elif D.USE_CUDA and FLAGS.model_type in ('transup', 'bprmf') and trainer.fused is not None \
-            and (FLAGS.model_type == 'bprmf' or FLAGS.embedding_size % 4 == 0) \
-            and os.environ.get('KTUP_FAST_TRAIN', '1') != '0':             # (a TUP width that is not a multiple of 4: the autograd route)
-        from jTransUP.utils.fast_train import DeviceFeeder, RecStepper
-        stepper = RecStepper(model, trainer, FLAGS, FLAGS.batch_size)
+    elif D.USE_CUDA and trainer.fused is not None and os.environ.get('KTUP_FAST_TRAIN', '1') != '0':
+        stepper_class = _stepper_class(FLAGS)
+    if stepper_class is not None:
+        from jTransUP.utils.fast_train import DeviceFeeder
+        stepper = stepper_class(model, trainer, FLAGS, FLAGS.batch_size)
         logger.info('GPU-resident training step enabled (KTUP_FAST_TRAIN=0 selects the autograd route).')
         if FLAGS.device_sampling:
             from jTransUP.utils.device_sampler import DeviceSampler
@@ -82,7 +95,7 @@ def train_loop(FLAGS, model, trainer, train_dataset, eval_datasets, user_total, 
             feed = DeviceFeeder(train_list, FLAGS.batch_size, D.DEV, FLAGS.negtive_samples, seed=FLAGS.seed)
             stepper.attach_feeds(sampler, rec=feed)
             logger.info('Training data and negative sampling are device-resident (-device_sampling).')
-    D.require_stepper_for_replicas(stepper, 'transup, bprmf')
+    D.require_stepper_for_replicas(stepper, 'transup, bprmf, fm')
     logger.info('Training.')
 
     def do_eval(totals):
@@ -120,6 +133,8 @@ def train_loop(FLAGS, model, trainer, train_dataset, eval_datasets, user_total, 
         u_var, pi_var, ni_var = D.ids(u), D.ids(pi), D.ids(ni)
         if stepper is not None and len(u) == stepper.GB:
             return 'rec', stepper.rec_step(u_var, pi_var, ni_var)
+        if stepper is not None and FLAGS.model_type == 'fm':
+            raise RuntimeError('training batch of unexpected size (MakeTrainIterator yields full batches)')
         trainer.optimizer_zero_grad()
         pos_score, neg_score = model(u_var, pi_var), model(u_var, ni_var)
         losses = bprLoss(pos_score, neg_score, target=trainer.model_target)

@@ -104,6 +104,11 @@ def evaluateKG(FLAGS, model, eval_head_iter, eval_tail_iter, eval_head_dict, eva
     return perf
 
 
+def _dot_step_supported(d):
+    from jTransUP.utils.fast_train_dot import dot_step_supported
+    return dot_step_supported(d)
+
+
 def train_loop(FLAGS, model, trainer, rating_train_dataset, triple_train_dataset, rating_eval_datasets, triple_eval_datasets, e_map,
                i_map, ikg_map, logger, vis=None, is_report=False):
     rating_train_iter, rating_train_total, rating_train_list, rating_train_dict = rating_train_dataset
@@ -117,7 +122,7 @@ def train_loop(FLAGS, model, trainer, rating_train_dataset, triple_train_dataset
     step_to_switch = 10 * FLAGS.joint_ratio          # :209 -- rec step iff step % 10 < 10 * joint_ratio
     # KTUP with its own tables: the step body below runs as ~a dozen C-ABI launches (utils/fast_train.py) instead of through
     # autograd; with -device_sampling the batches and their negatives never leave the GPU either.
-    stepper = rec_feed = kg_feed = sampler = None
+    stepper = rec_feed = kg_feed = sampler = baseline = None
     sharded = bool(getattr(FLAGS, 'shard_tables', False))
     if sharded:
         # BASELINE config 5: row-sharded user / item / entity tables, fixed-shape exchange, row-sparse Adagrad (utils/sharded_train.py)
@@ -155,7 +160,16 @@ def train_loop(FLAGS, model, trainer, rating_train_dataset, triple_train_dataset
             kg_feed = DeviceFeeder(triple_train_list, FLAGS.batch_size, D.DEV, FLAGS.negtive_samples, seed=FLAGS.seed + 1)
             stepper.attach_feeds(sampler, rec=rec_feed, kg=kg_feed)
             logger.info('Training data and negative sampling are device-resident (-device_sampling).')
-    D.require_stepper_for_replicas(stepper, 'jtransup, -noshare_embeddings')
+    elif D.USE_CUDA and FLAGS.model_type in ('cofm', 'cke') and trainer.fused is not None \
+            and os.environ.get('KTUP_FAST_TRAIN', '1') != '0' and _dot_step_supported(FLAGS.embedding_size):
+        # coFM / CKE: ktup_train_dot_step for the rec step, the existing TransE / TransR launches for the kg step, the alignment
+        # term (coFM with its own item table) on the device (utils/fast_train_dot.py)
+        from jTransUP.utils.fast_train_dot import BaselineJointStepper
+        stepper = baseline = BaselineJointStepper(model, trainer, FLAGS, FLAGS.batch_size)
+        logger.info('GPU-resident training step enabled (KTUP_FAST_TRAIN=0 selects the autograd route).')
+        if FLAGS.device_sampling:
+            logger.info('-device_sampling: the joint baselines take host-fed batches only; running as under -nodevice_sampling.')
+    D.require_stepper_for_replicas(stepper, 'jtransup -noshare_embeddings, cofm, cke')
     logger.info('Training.')
 
     def do_eval(totals):
@@ -215,6 +229,23 @@ def train_loop(FLAGS, model, trainer, rating_train_dataset, triple_train_dataset
             ph, pt, pr = kg_feed.next_cols()               # (h, t, r): tail before relation, like the files
             nh, nt = sampler.sample_kg(ph, pt, pr)
             return 'kg', stepper.kg_step(ph, pt, pr, nh, nt, pr)
+        if baseline is not None:                           # coFM / CKE: the id handling of the autograd route below, then the stepper
+            if is_rec:
+                u, pi, ni = getNegRatings(next(rating_train_iter), item_total, all_dicts=all_rating_dicts)
+                align = getMappedEntities(pi + ni, i_map, ikg_map) if baseline.align else None
+                if FLAGS.share_embeddings:
+                    ni = [i_map[i] for i in ni]; pi = [i_map[i] for i in pi]
+                if len(u) == stepper.GB:
+                    return 'rec', stepper.rec_step(D.ids(u), D.ids(pi), D.ids(ni), align=align)
+            else:
+                ph, pt, pr, nh, nt, nr = getTrainTripleBatch(next(triple_train_iter), entity_total, all_head_dicts=all_head_dicts,
+                                                             all_tail_dicts=all_tail_dicts)
+                align = getMappedItems(ph + pt + nh + nt, e_map, ikg_map) if baseline.align else None
+                if FLAGS.share_embeddings:
+                    ph, pt, nh, nt = ([e_map[e] for e in x] for x in (ph, pt, nh, nt))
+                if len(ph) == stepper.GB:
+                    return 'kg', stepper.kg_step(*(D.ids(x) for x in (ph, pt, pr, nh, nt, nr)), align=align)
+            raise RuntimeError('training batch of unexpected size (MakeTrainIterator yields full batches)')
         if stepper is not None:
             if is_rec:
                 u, pi, ni = getNegRatings(next(rating_train_iter), item_total, all_dicts=all_rating_dicts)

@@ -96,11 +96,13 @@ class ReplicaGradSync(object):
         raise ValueError(kind)
 
     @torch.no_grad()
-    def all_reduce_grads(self):
-        """ONE all-reduce(sum) of the flat bucket: no gather / scatter copies, the gradients are views into it."""
+    def all_reduce_grads(self, readopt=True):
+        """ONE all-reduce(sum) of the flat bucket: no gather / scatter copies, the gradients are views into it.
+        readopt=False: the caller writes the bucket itself and keeps some `.grad` at None on purpose (a table the optimizer is
+        not to step yet); no parameter is handed its view back."""
         if not _exchanging(self.group):
             return
-        for p in self.params:                 # autograd may have replaced a view by its own tensor (set_to_none, first backward)
+        for p in self.params if readopt else ():   # autograd may have replaced a view by its own tensor (set_to_none, first backward)
             if p.grad is None or p.grad.data_ptr() < self.flat.data_ptr() or \
                     p.grad.data_ptr() >= self.flat.data_ptr() + self.flat.numel() * 4:
                 self._readopt()

@@ -39,6 +39,7 @@ class _StepperBase(object):
 
     KINDS = ()        # step kinds of the subclass, e.g. ('rec', 'kg'), with the number of id tensors each takes
     N_IDS = {}
+    READOPT_GRADS = True      # the all-reduce hands a parameter whose `.grad` left the flat bucket its view back (False: a subclass keeps some at None)
 
     def __init__(self, model, trainer, FLAGS, batch_size, group=None, use_graphs=None):
         if trainer.fused is None:
@@ -99,7 +100,9 @@ class _StepperBase(object):
         # changes their norm), only with clipping on, and for d <= 128 (at d = 256 the rec step kernel has no registers left for the
         # returned values).  KTUP_TRACKED_NORM=0: the norm pass + grid barrier of round 2.
         self._gn = None
-        if self.world == 1 and self.max_norm > 0 and self.tabs[0].shape[1] <= 128 and _os.environ.get('KTUP_TRACKED_NORM', '1') != '0':
+        # (FM's and coFM's first parameter is their global bias, one element: their steps track no norm)
+        if self.world == 1 and self.max_norm > 0 and self.tabs[0].dim() == 2 and self.tabs[0].shape[1] <= 128 \
+                and _os.environ.get('KTUP_TRACKED_NORM', '1') != '0':
             self._gn = torch.zeros(64, dtype=torch.float64, device=dev)                 # KTUP_GNORM_WS_DOUBLES
         self._graphs = {}
         self._eager_steps = {k: 0 for k in self.KINDS}
@@ -380,7 +383,7 @@ class _StepperBase(object):
 
     def _optimizer_launches(self, loss=None, tracked=False):
         """`tracked`: the launch before this one was a fused step bound with the gradient-norm workspace."""
-        self.sync.all_reduce_grads()       # world > 1: gradients of all tables + the loss scalars, one bucket, one collective
+        self.sync.all_reduce_grads(readopt=self.READOPT_GRADS)   # world > 1: gradients of all tables + the loss scalars, one bucket, one collective
         self.trainer.fused.clip_and_step(self.max_norm, zero_grads=True, loss=loss, gnorm=self._gn_ptr() if tracked else None)
 
     def _fused_ok(self, kind, d, n_pref=0):

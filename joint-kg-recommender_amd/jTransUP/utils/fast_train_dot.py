@@ -1,0 +1,267 @@
+"""GPU-resident training steps of the inner-product recommenders: FM (item_recommendation.py:160-195 -> DotRecStepper) and the joint
+baselines coFM and CKE (knowledgable_recommendation.py:330-401 -> BaselineJointStepper), on the machinery of utils/fast_train.py
+(flat gradient bucket, data-parallel slice + all-reduce, pre-bound launches, HIP-graph replay, the K20 clip + step).
+
+Their rec step is one computation -- the inner product of a user row with an item-side row, optional bias terms, the BPR loss, the
+gradients back into the gathered rows -- and ONE launch: ktup_train_dot_step (include/ktup_dot_step.h), followed by
+ktup_optim_clip_step.  The kg side takes what exists: ktup_train_kg_step (TransE) for coFM, the TransR launches of KGStepper for
+CKE.  coFM with its own item table adds the alignment term of knowledgable_recommendation.py:385-390 to EVERY step:
+ktup_reg_align_pairs, whose id lists the host builds exactly as the autograd route does (getMappedEntities / getMappedItems on the
+global batch) and copies, with their length, into fixed buffers outside the graph.
+
+rec step:  bprLoss(pos, neg, target)                                                   [+ norm_lambda * pNormLoss(ent rows, item rows)]
+kg step:   kg_lambda * (marginLoss(pos, neg, margin) + normLoss(ent rows) + normLoss(rel rows))     [+ the same alignment term]
+"""
+import torch
+
+from jTransUP.hip import lib as L
+from jTransUP.utils.fast_train import _StepperBase, _p
+
+
+def dot_step_supported(d):
+    """Whether ktup_train_dot_step takes this width (and the library option `deterministic` is off): the drivers' condition."""
+    return bool(L.load().ktup_train_dot_step_supported(int(d)))
+
+
+class DotRecStepper(_StepperBase):
+    """FM: tables U, I, the two bias tables and the global bias; a step is ktup_train_dot_step + the optimizer launch.
+    loss slot 0: bpr.  The gradients of the user bias and the global bias are identically zero under a BPR loss (g - g): their
+    buffers stay zero-filled, and the optimizer applies its weight decay to them as on the autograd route.  A model without bias
+    tables (BPRMF) takes the same launch without the options (tools/dot_step_time.py; the drivers keep RecStepper for it)."""
+    KINDS = ('rec',)
+    N_IDS = {'rec': 3}
+
+    def _setup(self, FLAGS, f32, i64):
+        m = self.m
+        self.tabs = (m.user_embeddings.weight, m.item_embeddings.weight)
+        if hasattr(m, 'user_bias'):
+            self.tabs += (m.user_bias.weight, m.item_bias.weight, m.bias)
+        if not dot_step_supported(self.tabs[0].shape[1]):
+            raise L.KtupError('ktup_train_dot_step does not take embedding_size %d (or KTUP_DETERMINISTIC=1 is set)' % self.tabs[0].shape[1])
+        self._id_buffers('rec', i64)
+        self.gstate = None
+        self.fused_step = True
+
+    def _bind(self, st):
+        U, I = self.tabs[:2]
+        bu, bi, gb = self.tabs[2:] if len(self.tabs) > 2 else (None, None, None)
+        self.fused_step = True
+        self._rec_fused = L.bind('ktup_train_dot_step', _p(U), U.stride(0), _p(I), I.stride(0), None, 0, None, -1, _p(gb), _p(bu), _p(bi),
+                                 U.shape[1], _p(self.u2), _p(self.i2), self.B, self.target, 1.0 / self.world, _p(self.loss), _p(U.grad),
+                                 _p(I.grad), None, None if bi is None else _p(bi.grad), st)
+
+    def _rec_eager(self, u, pi, ni):
+        self._plans()
+        if u is not None:
+            self._pack('rec', (u, pi, ni))
+        self._rec_fused()
+        self._optimizer_launches(loss=(_p(self.loss), 1, 1.0, _p(self.out['rec']), self._acc_ptr('rec')))
+        return self.out['rec']
+
+    def rec_step(self, u, pi, ni):
+        """u, pi, ni: int64 device tensors of the GLOBAL batch.  Returns the step's loss (0-dim device tensor)."""
+        return self._step('rec', self._rec_eager, (u, pi, ni))
+
+
+class BaselineJointStepper(_StepperBase):
+    """coFM (either setting of -share_embeddings) and CKE.
+
+    A table joins the optimizer step with the first step that can give it a gradient, as on the autograd route, where a
+    parameter's `.grad` is None until its first backward and the optimizer skips it until then (no weight decay, no moment decay,
+    Adam's step count starts later): the relation table (and CKE's projections) wait for the first kg step, the user side for the
+    first rec step.  Until then their gradient views are kept aside; waking a table drops the captured graphs.
+
+    loss slots: rec 0 bpr | kg 0 margin, 2 normLoss(ent rows), 3 normLoss(rel rows) | 6 the alignment term (already scaled)."""
+    KINDS = ('rec', 'kg')
+    N_IDS = {'rec': 3, 'kg': 6}
+    ALIGN_SLOT = 6
+    READOPT_GRADS = False       # a sleeping table's `.grad` stays None through the all-reduce
+
+    def _setup(self, FLAGS, f32, i64):
+        m, B = self.m, self.B
+        self.kg_lambda, self.norm_lambda = float(FLAGS.kg_lambda), float(FLAGS.norm_lambda)
+        self.cke = hasattr(m, 'proj_embeddings')
+        U, E, R = m.user_embeddings.weight, m.ent_embeddings.weight, m.rel_embeddings.weight
+        I = m.item_embeddings.weight                                    # coFM -share_embeddings: the entity table itself
+        d = U.shape[1]
+        if not dot_step_supported(d):
+            raise L.KtupError('ktup_train_dot_step does not take embedding_size %d (or KTUP_DETERMINISTIC=1 is set)' % d)
+        self.gstate = None
+        self.lam = torch.full((), self.kg_lambda, **f32)               # upstream gradient of the multi-launch kg terms
+        self._id_buffers('rec', i64); self._id_buffers('kg', i64)
+        if self.cke:
+            M = m.proj_embeddings.weight
+            self.tabs = (U, I, E, R, M)
+            touch = {'rec': (U, I, E), 'kg': (E, R, M)}
+            nbytes = L.load().ktup_score_transr_workspace_bytes(2 * B, R.shape[0])
+            self.rws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=self.dev)
+            self.align = False
+            self.fused_step = False                                     # the TransR kg step is several launches: not device-fed
+        else:
+            bu, bi, gb = m.user_bias.weight, m.item_bias.weight, m.bias
+            shared = I is E
+            self.tabs = (U, bu, bi, gb, R, E) + (() if shared else (I,))
+            self.align = not shared                                     # :385-390, coFM with its own item table
+            touch = {'rec': (U, I, bu, bi, gb) + ((E,) if self.align else ()), 'kg': (E, R) + ((I,) if self.align else ())}
+            self.kg_fused = bool(self.want_fused and L.load().ktup_train_step_supported(2, d, 0))
+            self.fused_step = False                                     # host-fed only: the alignment lists are built on the host
+        self._touch = touch
+        self._views = {id(t): t.grad for t in self.tabs}                # ReplicaGradSync's views into the flat bucket
+        self._awake = set()
+        for t in self.tabs:
+            t.grad = None
+        if self.align:
+            # [n | entity ids (cap) | item ids (cap)]: a kg step lists up to 4 x GB distinct entities, a rec step up to 2 x GB items
+            self.al_cap = 4 * self.GB
+            self._al = torch.zeros(1 + 2 * self.al_cap, **i64)
+            self._al_host = torch.zeros(1 + 2 * self.al_cap, dtype=torch.int64).pin_memory()      # staging, filled in place
+            self._al_np = self._al_host.numpy()
+            self._al_copied = torch.cuda.Event()
+            self.total = {k: torch.zeros((), **f32) for k in self.KINDS}
+
+    # ------------------------------------------------------------------------------------------------ late tables
+    def _g(self, t):
+        return self._views[id(t)].data_ptr()
+
+    def _wake(self, kind):
+        new = [t for t in self._touch[kind] if id(t) not in self._awake]
+        if not new:
+            return
+        for t in new:
+            t.grad = self._views[id(t)]
+            self._awake.add(id(t))
+        torch.cuda.current_stream(self.dev).synchronize()               # a replay may still be running (at most twice per run)
+        self._graphs = {}                                               # captured with the shorter table list of the optimizer launch
+        self._eager_steps = {k: 0 for k in self.KINDS}
+        self._keys = None
+        self.trainer.fused._plan = None
+
+    def _plans(self):
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        keys = tuple(t.data_ptr() for t in self.tabs) + tuple(self._g(t) for t in self.tabs)
+        if self._keys != keys or st != self._stream:
+            self._keys, self._stream = keys, st
+            self._bind(st)
+
+    def attach_feeds(self, sampler, **feeds):
+        raise L.KtupError('the joint baselines take host-fed batches only')
+
+    def can_feed(self, kind):
+        return False
+
+    # ------------------------------------------------------------------------------------------------ launch plans
+    def _bind(self, st):
+        m, B, b, g = self.m, self.B, L.bind, self._g
+        inv = 1.0 / self.world
+        pos, neg, gpos, gneg = self.score[:B], self.score[B:], self.gscore[:B], self.gscore[B:]
+        if self.cke:
+            U, I, E, R, M = self.tabs
+            d = U.shape[1]
+            self._rec_fused = b('ktup_train_dot_step', _p(U), U.stride(0), _p(I), I.stride(0), _p(E), E.stride(0), _p(m._item2ent),
+                                m.ent_total - 1, None, None, None, d, _p(self.u2), _p(self.i2), B, self.target, inv, _p(self.loss),
+                                g(U), g(I), g(E), None, st)
+            # the TransR sequence of KGStepper._bind, with kg_lambda as the upstream scalar
+            self._kg = [
+                b('ktup_score_transr_fwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0), min(R.shape[0], M.shape[0]), d,
+                  _p(self.h2), _p(self.t2), _p(self.r2), 2 * B, self.l1, _p(self.score), _p(self.rws), st),
+                b('ktup_loss_margin_fused', _p(pos), _p(neg), B, self.margin, _p(self.lam), _p(self.loss[0:]), _p(gpos), _p(gneg), st),
+                b('ktup_score_transr_bwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0), d, _p(self.h2), _p(self.t2),
+                  _p(self.r2), 2 * B, self.l1, _p(self.gscore), g(E), g(R), g(M), st),
+                b('ktup_reg_norm_fused', _p(E), E.stride(0), d, _p(self.ht4), 4 * B, _p(self.lam), _p(self.loss[2:]), g(E), st),
+                b('ktup_reg_norm_fused', _p(R), R.stride(0), d, _p(self.r2), 2 * B, _p(self.lam), _p(self.loss[3:]), g(R), st)]
+            return
+        U, bu, bi, gb, R, E = self.tabs[:6]
+        I = self.tabs[6] if self.align else E
+        d = U.shape[1]
+        self._rec_fused = b('ktup_train_dot_step', _p(U), U.stride(0), _p(I), I.stride(0), None, 0, None, -1, _p(gb), _p(bu), _p(bi), d,
+                            _p(self.u2), _p(self.i2), B, self.target, inv, _p(self.loss), g(U), g(I), None, g(bi), st)
+        if self.kg_fused:
+            self._kg_fused = b('ktup_train_kg_step', 0, _p(E), E.stride(0), _p(R), R.stride(0), None, 0, d, _p(self.h2), _p(self.t2),
+                               _p(self.r2), B, self.l1, self.margin, self.kg_lambda, 6, _p(self.loss), g(E), g(R), None, None, st)
+        # (a width ktup_train_kg_step does not take, d % 4 != 0: the TransE sequence of KGStepper._bind)
+        self._kg = [
+            b('ktup_score_transe_fwd', _p(E), E.stride(0), _p(R), R.stride(0), R.shape[0], d, _p(self.h2), _p(self.t2), _p(self.r2), 2 * B,
+              self.l1, _p(self.score), st),
+            b('ktup_loss_margin_fused', _p(pos), _p(neg), B, self.margin, _p(self.lam), _p(self.loss[0:]), _p(gpos), _p(gneg), st),
+            b('ktup_score_transe_bwd', _p(E), E.stride(0), _p(R), R.stride(0), d, _p(self.h2), _p(self.t2), _p(self.r2), 2 * B, self.l1,
+              _p(self.gscore), g(E), g(R), st),
+            b('ktup_reg_norm_fused', _p(E), E.stride(0), d, _p(self.ht4), 4 * B, _p(self.lam), _p(self.loss[2:]), g(E), st),
+            b('ktup_reg_norm_fused', _p(R), R.stride(0), d, _p(self.r2), 2 * B, _p(self.lam), _p(self.loss[3:]), g(R), st)]
+        if self.align:
+            cap = self.al_cap
+            # every rank applies the whole term (the lists come from the global batch), scaled 1 / world like the other replicated terms
+            self._align = b('ktup_reg_align_pairs', _p(E), E.stride(0), _p(I), I.stride(0), d, _p(self._al[1:]), _p(self._al[1 + cap:]),
+                            _p(self._al), -1, cap, self.l1, self.norm_lambda * inv, _p(self.loss[self.ALIGN_SLOT:]), g(E), g(I), st)
+
+    # ------------------------------------------------------------------------------------------------ alignment lists
+    def set_alignment(self, e_ids, i_ids):
+        """The aligned (entity, item) pairs of the NEXT step (getMappedEntities / getMappedItems on the global batch): copied, with
+        their number, into the fixed buffers ktup_reg_align_pairs reads -- one host-to-device copy, outside the graph."""
+        n = len(e_ids)
+        if n != len(i_ids) or n > self.al_cap:
+            raise L.KtupError('%d / %d alignment ids for buffers of %d' % (n, len(i_ids), self.al_cap))
+        cap, host = self.al_cap, self._al_np
+        self._al_copied.synchronize()                                   # the previous step's copy has left the staging buffer
+        host[0] = n
+        host[1:1 + n] = e_ids
+        host[1 + cap:1 + cap + n] = i_ids
+        self._al[:1 + cap + n].copy_(self._al_host[:1 + cap + n], non_blocking=True)
+        self._al_copied.record()
+
+    def _finish(self, kind, n_slots, scale):
+        """Alignment launch (own item table), optimizer launch, the step's loss."""
+        if self.align:
+            self._align()
+        self._optimizer_launches(loss=(_p(self.loss), n_slots, scale, _p(self.out[kind]), None))
+        if not self.align:
+            return self.out[kind]
+        # the alignment term is not part of what kg_lambda scales: its slot is folded in, and cleared, here
+        torch.add(self.out[kind], self.loss[self.ALIGN_SLOT], out=self.total[kind])
+        self.loss[self.ALIGN_SLOT:self.ALIGN_SLOT + 1].zero_()
+        return self.total[kind]
+
+    # ------------------------------------------------------------------------------------------------ steps
+    def _rec_eager(self, u, pi, ni):
+        self._plans()
+        if u is not None:
+            self._pack('rec', (u, pi, ni))
+        self._rec_fused()
+        return self._finish('rec', 1, 1.0)
+
+    def _kg_eager(self, ph, pt, pr, nh, nt, nr):
+        self._plans()
+        if ph is not None:
+            self._pack('kg', (ph, pt, pr, nh, nt, nr))
+        if not self.cke and self.kg_fused:
+            self._kg_fused()
+            return self._finish('kg', 4, self.kg_lambda)
+        for launch in self._kg:                                         # gradients x kg_lambda (device scalar), slots unscaled
+            launch()
+        return self._finish('kg', 4, self.kg_lambda)
+
+    def rec_step(self, u, pi, ni, align=None):
+        """u, pi, ni: int64 device tensors of the GLOBAL batch (coFM -share_embeddings: pi, ni already mapped to entity rows).
+        align = (entity ids, item ids), coFM with its own item table only.  Returns the step's loss (0-dim device tensor)."""
+        self._wake('rec')
+        self._take_alignment(align)
+        return self._step('rec', self._rec_eager, (u, pi, ni))
+
+    def kg_step(self, ph, pt, pr, nh, nt, nr, align=None):
+        self._wake('kg')
+        self._take_alignment(align)
+        if self.cke:
+            # Never captured: the relation-bucketed TransR kernels (d = 64, 100, 128) clear their counters in the workspace with
+            # hipMemsetAsync, and a captured memset node whose destination lies inside a pooled allocation writes garbage from its
+            # second replay on -- the bucket kernels then index past the workspace.  The rec step replays.
+            out = self._kg_eager(ph, pt, pr, nh, nt, nr)
+            self.trainer.step += 1
+            return out
+        return self._step('kg', self._kg_eager, (ph, pt, pr, nh, nt, nr))
+
+    def _take_alignment(self, align):
+        if self.align:
+            if align is None:
+                raise L.KtupError('coFM with its own item table: every step takes its alignment lists (align=)')
+            self.set_alignment(*align)
+        elif align is not None and (len(align[0]) or len(align[1])):
+            raise L.KtupError('this model has no alignment term')

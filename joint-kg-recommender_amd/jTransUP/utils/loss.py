@@ -37,7 +37,8 @@ def bprLoss(pos, neg, target=1.0):
 
 
 def pNormLoss(emb1, emb2, L1_flag=False):
-    """utils/loss.py:33-38 -- only used by the cofm/cfkg alignment term (out of scope models); plain tensor ops."""
+    """utils/loss.py:33-38 -- the alignment term of coFM / CFKG on the autograd route (plain tensor ops).  coFM's GPU-resident step
+    computes the same term and its gradients with ktup_reg_align_pairs (utils/fast_train_dot.py); CFKG keeps this route."""
     import torch
     distance = torch.sum(torch.abs(emb1 - emb2), 1) if L1_flag else torch.sum((emb1 - emb2) ** 2, 1)
     return distance.mean()

@@ -1,0 +1,110 @@
+"""The training step of the inner-product recommenders without a GPU: the extension header against the built library and the
+binding table, the width query, and host-side argument validation of the two entry points (no launch is made)."""
+import ctypes
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, 'include', 'ktup_dot_step.h')
+ERR_INVALID, ERR_UNSUPPORTED = -1, -3
+
+
+def declared_symbols(path):
+    text = open(path).read()
+    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    return sorted(set(re.findall(r'\b(ktup_[a-z0-9_]+)\s*\(', text)))
+
+
+@pytest.fixture(scope='module')
+def lib():
+    from jTransUP.hip import lib as L
+    if not os.path.exists(L.LIB_PATH):
+        import importlib.util
+        spec = importlib.util.spec_from_file_location('build_hip', os.path.join(ROOT, 'joint-kg-recommender_amd', 'build_hip.py'))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        mod.build(verbose=False)
+    return L
+
+
+def test_extension_header_library_and_binding_table_agree(lib):
+    syms = declared_symbols(HEADER)
+    assert syms == ['ktup_reg_align_pairs', 'ktup_train_dot_step', 'ktup_train_dot_step_supported']
+    handle = ctypes.CDLL(lib.LIB_PATH)
+    missing = [s for s in syms if not hasattr(handle, s)]
+    assert not missing, 'declared in include/ktup_dot_step.h but not exported: %s' % missing
+    assert sorted(lib.SIGNATURES_DOT_STEP) == syms
+    for other in (lib.SIGNATURES, lib.SIGNATURES_TRANSD, lib.SIGNATURES_DOT):
+        assert not set(other) & set(lib.SIGNATURES_DOT_STEP)
+    loaded = lib.load()
+    for s in syms:
+        assert getattr(loaded, s).argtypes == lib.SIGNATURES_DOT_STEP[s]
+        assert getattr(loaded, s).restype is ctypes.c_int
+    # the argument counts of the declarations
+    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
+    for s in syms:
+        args = re.search(r'\b%s\s*\(([^)]*)\)' % s, text).group(1)
+        assert len(args.split(',')) == len(lib.SIGNATURES_DOT_STEP[s]), s
+
+
+def test_supported_widths(lib):
+    loaded = lib.load()
+    assert [loaded.ktup_train_dot_step_supported(d) for d in (1, 50, 256)] == [1, 1, 1]
+    assert [loaded.ktup_train_dot_step_supported(d) for d in (0, 257)] == [0, 0]
+
+
+def test_the_option_deterministic_declines(lib):
+    loaded = lib.load()
+    old = lib.set_option('deterministic', 1)
+    try:
+        assert loaded.ktup_train_dot_step_supported(50) == 0
+        with pytest.raises(lib.KtupError) as e:
+            lib.call('ktup_train_dot_step', 64, 64, 64, 64, None, 0, None, -1, None, None, None, 64, 64, 64, 5, 1.0, 1.0, 64, 64, 64,
+                     None, None, None)
+        assert e.value.code == ERR_UNSUPPORTED
+    finally:
+        lib.set_option('deterministic', old)
+    assert loaded.ktup_train_dot_step_supported(50) == 1
+
+
+def test_host_side_validation_of_the_step_entry_point(lib):
+    """Every rejection happens before any launch (no GPU needed).  `p`: a non-null, 16-byte aligned dummy, validated, never
+    dereferenced on the host."""
+    p = 64
+
+    def status(U=p, ldu=64, I=p, ldi=64, X=None, ldx=0, xmap=None, d=64, u=p, i=p, B=5, loss=p, gU=p, gI=p, gX=None):
+        with pytest.raises(lib.KtupError) as e:
+            lib.call('ktup_train_dot_step', U, ldu, I, ldi, X, ldx, xmap, -1, None, None, None, d, u, i, B, 1.0, 1.0, loss, gU, gI, gX,
+                     None, None)
+        assert 'ktup_train_dot_step' in str(e.value)
+        return e.value.code
+
+    assert status(B=0) == ERR_INVALID
+    assert status(U=None) == ERR_INVALID
+    assert status(X=p, ldx=64, gX=p) == ERR_INVALID             # a second item-side table without its map
+    assert status(xmap=p) == ERR_INVALID                        # and the other way round
+    assert status(X=p, ldx=64, xmap=p) == ERR_INVALID           # ... without its gradient
+    assert status(d=0) == ERR_INVALID
+    assert status(ldi=63) == ERR_INVALID                        # a pitch below the width
+    assert status(loss=None) == ERR_INVALID
+    assert status(gI=None) == ERR_INVALID
+    assert status(d=257, ldu=257, ldi=257) == ERR_UNSUPPORTED
+    assert lib.ERR_UNSUPPORTED == ERR_UNSUPPORTED
+
+
+def test_host_side_validation_of_the_alignment_entry_point(lib):
+    p = 64
+
+    def rc(A=p, lda=36, B=p, ldb=36, d=36, a=p, b=p, n_dev=p, n_host=-1, cap=16, loss=p, gA=p, gB=p):
+        return lib.load().ktup_reg_align_pairs(A, lda, B, ldb, d, a, b, n_dev, n_host, cap, 1, 1.0, loss, gA, gB, None)
+
+    assert rc(n_host=17) == ERR_INVALID                         # more pairs than the fixed buffers hold, where the host knows
+    assert rc(d=0) == ERR_INVALID
+    assert rc(A=None) == ERR_INVALID
+    assert rc(n_dev=None) == ERR_INVALID
+    assert rc(lda=35) == ERR_INVALID
+    assert rc(cap=-1) == ERR_INVALID
+    assert rc(n_host=0) == 0                                    # nothing to add: no launch
+    assert rc(cap=0, n_host=-1) == 0
