@@ -753,6 +753,122 @@ int ktup_optim_clip_step(int kind, int n_tensors, float* const* params, float* c
                          float alpha, double* ws, double* gnorm, float max_norm, int zero_grads, float* loss_slots, int n_slots,
                          float loss_scale, float* loss_out, float* loss_acc, void* stream);
 
+/* =================================================================== TransD
+ * The reference's jTransUP/models/transD.py (its class is called TransHModel there, a copy-paste leftover) with the projection of
+ * jTransUP/utils/misc.py:36-37 (projection_transD_pytorch_samesize):
+ *     e_perp = e + (e . e_p) r_p
+ * Four tables, all d wide: E (ent_embeddings), R (rel_embeddings), Ep (ent_proj_embeddings), Rp (rel_proj_embeddings).
+ * Kernels: csrc/ktup_transd_score.hip, csrc/ktup_transd_eval.hip.                                                              */
+/* ------------------------------------------------------------------ TransD score  transD.py:61-76
+ * score[i] = dist( h_perp + r - t_perp ),  dist = sum |.| (l1) or sum (.)^2.  Any d >= 1, any pitches.                     */
+int ktup_score_transd_fwd(const float* E, int64_t lde, const float* R, int64_t ldr, const float* Ep, int64_t ldep,
+                          const float* Rp, int64_t ldrp, int d, const int64_t* h, const int64_t* t, const int64_t* r,
+                          int64_t n, int l1, float* score, void* stream);
+/* autograd of the above (torch.abs differentiates to sign with sign(0) = 0):  with v = h_perp + r - t_perp, g = gscore dist'(v),
+ * alpha = h.h_p, beta = t.t_p, gamma = g.r_p:
+ *   gE[h] += g + gamma h_p    gEp[h] += gamma h    gE[t] += -g - gamma t_p    gEp[t] += -gamma t
+ *   gR[r] += g                gRp[r] += (alpha - beta) g                                                                    */
+int ktup_score_transd_bwd(const float* E, int64_t lde, const float* R, int64_t ldr, const float* Ep, int64_t ldep,
+                          const float* Rp, int64_t ldrp, int d, const int64_t* h, const int64_t* t, const int64_t* r,
+                          int64_t n, int l1, const float* gscore, float* gE, float* gR, float* gEp, float* gRp, void* stream);
+
+/* ------------------------------------------------------------------ all-entity scores  transD.py:78-134
+ * out[i * ldo + j] = dist( c_i - e_j - (e_j . a_i) b_i ),  e_j = row j of the candidate table C (normally E, or a slice of it),
+ * a_i = Ep[q[i]] (EVERY candidate is projected with the QUERY entity's projection vector, transD.py:94-98), b_i = Rp[r[i]],
+ * c_i = q_perp - r (head != 0, evaluateHead) or q_perp + r (evaluateTail; the reference names an undefined t_proj_expand at
+ * transD.py:127 and raises NameError -- the h_proj_expand it computes two lines above is what is implemented here).
+ * Squared L2 at d in {20, 36, 64, 100, 128} with 16-byte aligned candidate rows runs on the matrix cores (option "eval_mc" = 0:
+ * the pair kernel); L1 and every other width take the pair kernel.  ws: ktup_eval_transd_workspace_bytes(d, nq) bytes, 16-byte
+ * aligned.                                                                                                                  */
+size_t ktup_eval_transd_workspace_bytes(int d, int64_t nq);
+int ktup_eval_transd_scores(const float* E, int64_t lde, const float* Ep, int64_t ldep, const float* R, int64_t ldr,
+                            const float* Rp, int64_t ldrp, int d, const float* C, int64_t ldc, int64_t n_cand,
+                            const int64_t* q, const int64_t* r, int64_t nq, int l1, int head, float* out, int64_t ldo,
+                            float* ws, void* stream);
+
+/* ------------------------------------------------------------------ a whole link-prediction pass
+ * knowledge_representation.py:93-146 + utils/misc.py:61-146 for TransD; the contract of ktup_eval_kg_ranks above: all nq
+ * keys at once, CSR gold / filter lists with ABSOLUTE offsets (nq + 1 entries), `chunk` keys scored at a time into `ws`
+ * (ktup_eval_kg_ranks_transd_workspace_bytes) and ranked by ktup_eval_gold_ranks; ranks[g] = filtered 0-based rank of gold entry g,
+ * -1 for a gold id that is itself filtered.                                                                                 */
+size_t ktup_eval_kg_ranks_transd_workspace_bytes(int d, int64_t n_cand, int64_t chunk);
+int ktup_eval_kg_ranks_transd(const float* E, int64_t lde, const float* Ep, int64_t ldep, const float* R, int64_t ldr,
+                              const float* Rp, int64_t ldrp, int d, const float* C, int64_t ldc, int64_t n_cand,
+                              const int64_t* q, const int64_t* r, int64_t nq, int l1, int head, int descending,
+                              const int64_t* filt_off, const int32_t* filt_ids, const int64_t* gold_off,
+                              const int32_t* gold_ids, int32_t* ranks, int64_t chunk, void* ws, void* stream);
+
+/* =================================================================== inner-product evaluation pass (csrc/ktup_dot_pass.hip)
+ * The whole-pass evaluation of the inner-product recommenders (BPRMF bprmf.py:51-54, FM fm.py:69-80, CKE CKE.py:142-153 and coFM
+ * cofm.py:127-141): all-item scores AND the filtered top-n of every user in one sweep that never writes the (users x items)
+ * matrix -- what ktup_eval_bprmf_scores + the bias adds + ktup_eval_topk_filtered(descending) compute batch by batch.          */
+/* ------------------------------------------------------------------ scores + filtered top-n of a whole pass
+ * score(b, j) = (U[u_ids[b]] . I[j] + user_add[b]) + item_add[j]
+ * The dot product is the fp32 fma chain over k = 0 .. d-1 starting from +0 (the bits of ktup_eval_bprmf_scores); the two additions
+ * are separately rounded fp32 adds in that order, a NULL term is skipped -- the bits of
+ *     gemm + (bias + user_bias[u])[:, None] + item_bias[None, :]
+ * The ranked list is that of ktup_eval_topk_filtered(scores, descending = 1): descending score, ties -> lower id, ids of the
+ * user's filter list skipped, -1 padding; top_scores (may be NULL) holds the scores themselves, 0 in padded slots.
+ *
+ * Any 1 <= d <= 256 (rows that are not 16-byte aligned or d % 4 != 0 are loaded element by element), any pitches, topn <= 16,
+ * n_items < 2^31, duplicates in u_ids allowed; otherwise KTUP_ERR_UNSUPPORTED and the caller keeps the per-batch calls.
+ * user_add: nq floats, the term of user b of u_ids; item_add: n_items floats.  filt_off / filt_ids: CSR filter sets per user of
+ * u_ids (filt_off[nq + 1]; NULL = none).  nsplit: into how many contiguous parts the catalogue is cut (each part of a block of 64
+ * users is one workgroup); 0 = chosen by the library, a larger request than the merge takes (512 / topn, at most 32) or the
+ * catalogue yields is reduced.  `ws`: ktup_eval_dot_topk_workspace_bytes bytes for the same arguments, 16-byte aligned.       */
+size_t ktup_eval_dot_topk_workspace_bytes(int d, int64_t nq, int64_t n_items, int topn, int nsplit);
+int ktup_eval_dot_topk(const float* U, int64_t ldu, const float* I, int64_t ldi, int d, const int64_t* u_ids, int64_t nq,
+                       int64_t n_items, const float* user_add, const float* item_add, const int64_t* filt_off,
+                       const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids, float* top_scores, void* ws,
+                       void* stream);
+
+/* =================================================================== training step of the inner-product recommenders
+ * (csrc/ktup_dot_step.hip)  The rec step of FM (fm.py:58-67), coFM (cofm.py:99-108) and CKE (CKE.py:122-135) -- and of BPRMF, which
+ * is the same thing without the options -- is one computation: the inner product of a user row with an item-side row, optional
+ * bias terms, the BPR loss over (positive, negative) pairs and the gradients back into the gathered rows.  ktup_train_dot_step does
+ * all of it in ONE launch (ktup_optim_clip_step follows, as after ktup_train_rec_step / ktup_train_kg_step); ktup_reg_align_pairs is
+ * the alignment term of the joint baselines (knowledgable_recommendation.py:385-390, utils/loss.py:33-38 pNormLoss) on the device. */
+/* ------------------------------------------------------------------ the rec step of FM / coFM / CKE (/ BPRMF) in one launch
+ * u_ids = [u ; u] and i_ids = [pos ; neg], 2B entries each (the layout ktup_feed_rec fills): rows k and k + B are the positive
+ * and the negative pair of example k; only the first B entries of u_ids are read.  For each of the 2B pairs
+ *     s = ((gbias[0] + bu[u]) + bi[i]) + dot(U[u], V(i)),     V(i) = I[i]   or   I[i] + X[x_of_item[i]]
+ * (the additions of fm.py:45 / cofm.py:45 in their order; the second form is CKE.py:63).  Each of gbias, bu, bi and X may be NULL:
+ * the term is then absent.  X needs x_of_item (int64, one entry per row of I) and the other way round.
+ *     loss[0] += up * mean_k( -logsigmoid(target * (s_pos[k] - s_neg[k])) )        (evaluated as max(-x, 0) + log1p(exp(-|x|)))
+ * and with g_k the derivative of that term with respect to s_pos[k] (-g_k is the one with respect to s_neg[k]) the gradients
+ * are ADDED (float atomics; duplicate users and items in a batch are fine) to buffers with the pitches of their tables:
+ *     gU[u] += g (V(pos) - V(neg))                 one row add per example: a user is shared by its positive and its negative
+ *     gI[pos] += g U[u],   gI[neg] -= g U[u]
+ *     gX[x_of_item[pos]] += g U[u],  gX[x_of_item[neg]] -= g U[u]      except for row x_pad: the gradient-free padding row of
+ *                                                                      nn.Embedding(padding_idx) is never written
+ *     gbi[pos] += g,  gbi[neg] -= g                (gbi may be NULL although bi is given)
+ * The gradients of bu and gbias are g + (-g): identically zero under a BPR loss, hence no arguments.  `up`: upstream scalar of the
+ * loss (1 / world for data-parallel replicas).
+ *
+ * Any B >= 1 and 1 <= d <= 256; rows that are 16-byte aligned with d % 4 == 0 (pointers and pitches of every table and gradient)
+ * are loaded as float4, others element by element.  Larger d, or the library option "deterministic" being set (the row adds are
+ * float atomics issued by many workgroups), is KTUP_ERR_UNSUPPORTED: the caller keeps its multi-launch route.
+ * ktup_train_dot_step_supported(d): 1 if a launch with this width would be taken (no launch is made), else 0.                  */
+int ktup_train_dot_step_supported(int d);
+int ktup_train_dot_step(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* X, int64_t ldx,
+                        const int64_t* x_of_item, int64_t x_pad, const float* gbias, const float* bu, const float* bi, int d,
+                        const int64_t* u_ids, const int64_t* i_ids, int64_t B, float target, float up, float* loss, float* gU,
+                        float* gI, float* gX, float* gbi, void* stream);
+
+/* ------------------------------------------------------------------ alignment term of the joint baselines
+ *     loss[0] += scale * mean_{k < n}( sum_j |A[a_ids[k]][j] - B[b_ids[k]][j]| )            (l1 != 0; else the squared differences)
+ * and the gradients of that term are ADDED to gA (pitch lda) and gB (pitch ldb): scale / n * sign(a - b) with sign(0) = 0, as
+ * torch.abs differentiates, or scale / n * 2 (a - b); gB takes the negative.
+ * n is read from DEVICE memory (*n_dev, one int64): the id lists live in fixed buffers of capacity `cap`, so a captured graph
+ * replays with a different list length every step.  The kernel clamps n to cap.  n_host: the same length where the host knows it,
+ * else -1; n_host > cap is KTUP_ERR_INVALID_ARG.
+ * n == 0 adds NOTHING (loss and gradients untouched).  The autograd route's mean over an empty list is NaN there, as the
+ * reference's; that is deliberately not reproduced.
+ * Any d >= 1, any pitches, duplicate ids allowed.                                                                              */
+int ktup_reg_align_pairs(const float* A, int64_t lda, const float* B, int64_t ldb, int d, const int64_t* a_ids,
+                         const int64_t* b_ids, const int64_t* n_dev, int64_t n_host, int64_t cap, int l1, float scale, float* loss,
+                         float* gA, float* gB, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,29 +21,19 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-ato
 # for the kernels that feed FMAs from SGPRs.
 PER_FILE_FLAGS = {'ktup_score_pref.hip': ['-fno-slp-vectorize'], 'ktup_eval.hip': ['-fno-slp-vectorize'],
                   'ktup_transd_eval.hip': ['-fno-slp-vectorize']}
-# Extension directories under csrc/, each with its own C header under include/: compiled into the same library (objects are
-# prefixed with the directory's name).  csrc/*.hip itself stays the set of translation units the committed profiles were taken from.
-EXTENSIONS = {'transd': 'ktup_transd.h', 'dot': 'ktup_dot.h', 'dotstep': 'ktup_dot_step.h'}
 
 
 def _sources():
-    srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
-    for ext in sorted(EXTENSIONS):
-        srcs += sorted(os.path.join(CSRC, ext, f) for f in os.listdir(os.path.join(CSRC, ext)) if f.endswith('.hip'))
-    return srcs
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.hip'))
 
 
 def _headers():
     inc = os.path.join(os.path.dirname(HERE), 'include')
-    hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + [os.path.join(inc, 'ktup_hip.h')]
-    for ext, header in sorted(EXTENSIONS.items()):
-        hdrs += [os.path.join(CSRC, ext, f) for f in os.listdir(os.path.join(CSRC, ext)) if f.endswith('.h')] + [os.path.join(inc, header)]
-    return hdrs
+    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')] + [os.path.join(inc, 'ktup_hip.h')]
 
 
 def _obj(src):
-    sub = os.path.relpath(os.path.dirname(src), CSRC)
-    return os.path.join(OBJ, ('' if sub == '.' else sub.replace(os.sep, '_') + '_') + os.path.basename(src)[:-4] + '.o')
+    return os.path.join(OBJ, os.path.basename(src)[:-4] + '.o')
 
 
 def _stale(target, deps):

@@ -19,117 +19,20 @@
 //     float compare; the keys decide equality, NaNs and a list that is still short) and its bit in the pass's filter bitmap (built
 //     once per pass from the CSR lists, read from L2 by candidates only) is clear;
 //   * the splits' partial lists are merged by a last, tiny launch.
-// The key, list and merge helpers are a small copy of those in the anonymous namespace of ktup_eval_pass.hip (a profiled
-// translation unit, which stays byte-identical): to be merged at the next profile collection.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "../ktup_common.h"
-#include "../ktup_lane_swap.h"
-#include "../../../include/ktup_dot.h"
+#include "ktup_common.h"
+#include "ktup_lane_swap.h"
+#include "ktup_topn.h"
 
 namespace ktup {
 namespace {
 
-constexpr uint64_t PKEY_MAX = ~0ull;
-constexpr int TOPN_MAX = 16;     // top-n list capacity per user: one element per lane of a 16-lane row
-constexpr int PCAP = 32;         // pending candidates per user between two merges (a merge is due at 16; one tile adds at most 16)
-constexpr int NSPLIT_MAX = 32;   // catalogue splits: NSPLIT_MAX * TOPN_MAX keys per user is what the merge holds
-constexpr int MERGE_KEYS = NSPLIT_MAX * TOPN_MAX;
+constexpr int NSPLIT_MAX = 32;   // catalogue splits: NSPLIT_MAX * TOPN_MAX keys per user is what the merge holds, eight per lane
+constexpr int MERGE_PER_LANE = NSPLIT_MAX * TOPN_MAX / 64;
 constexpr size_t WAVE_LDS = (size_t)16 * PCAP * 8 + (size_t)16 * 16 * 8;   // pending rows | lists
-
-KTUP_DEV uint64_t pass_key(float s, uint32_t id) {   // ktup_rank.hip make_key, ascending (the caller negates)
-  if (s == 0.f) s = 0.f;
-  uint32_t u = __float_as_uint(s);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | id;
-}
-
-// ---- 16-lane row networks on 64-bit keys (lane j of a row = element j).  Partner j ^ K through DPP: quad_perm for 1 and 2,
-// row_half_mirror . quad_perm[3,2,1,0] for 4, row_mirror . row_half_mirror for 8.
-template <int K>
-KTUP_DEV uint32_t row_xor32(uint32_t v) {
-  const int x = (int)v;
-  if constexpr (K == 1) return (uint32_t)__builtin_amdgcn_update_dpp(x, x, 0xB1, 0xf, 0xf, false);
-  else if constexpr (K == 2) return (uint32_t)__builtin_amdgcn_update_dpp(x, x, 0x4E, 0xf, 0xf, false);
-  else if constexpr (K == 4) {
-    const int h = __builtin_amdgcn_update_dpp(x, x, 0x141, 0xf, 0xf, false);
-    return (uint32_t)__builtin_amdgcn_update_dpp(h, h, 0x1B, 0xf, 0xf, false);
-  } else {
-    const int m = __builtin_amdgcn_update_dpp(x, x, 0x140, 0xf, 0xf, false);
-    return (uint32_t)__builtin_amdgcn_update_dpp(m, m, 0x141, 0xf, 0xf, false);
-  }
-}
-template <int K>
-KTUP_DEV void row_cmpx(uint64_t& v, bool keep_min) {   // compare-exchange with lane j ^ K
-  const uint64_t o = ((uint64_t)row_xor32<K>((uint32_t)(v >> 32)) << 32) | row_xor32<K>((uint32_t)v);
-  if ((o < v) == keep_min) v = o;
-}
-KTUP_DEV uint64_t row_mirror64(uint64_t v) {
-  const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_update_dpp(hi, hi, 0x140, 0xf, 0xf, false) << 32) |
-         (uint32_t)__builtin_amdgcn_update_dpp(lo, lo, 0x140, 0xf, 0xf, false);
-}
-// list: a row's ascending 16 keys; cand: up to 16 more in any order (PKEY_MAX = none).  Returns the 16 smallest of the 32, ascending:
-// bitonic sort of the candidates, elementwise min against their mirror, bitonic merge.
-KTUP_DEV uint64_t row_merge16(uint64_t list, uint64_t cand, int j) {
-  const bool b1 = (j & 1) == 0, b2 = (j & 2) == 0, b4 = (j & 4) == 0, b8 = (j & 8) == 0;
-  row_cmpx<1>(cand, b1 == b2);
-  row_cmpx<2>(cand, b2 == b4); row_cmpx<1>(cand, b1 == b4);
-  row_cmpx<4>(cand, b4 == b8); row_cmpx<2>(cand, b2 == b8); row_cmpx<1>(cand, b1 == b8);
-  row_cmpx<8>(cand, b8); row_cmpx<4>(cand, b4); row_cmpx<2>(cand, b2); row_cmpx<1>(cand, b1);
-  const uint64_t r = row_mirror64(cand);
-  uint64_t m = r < list ? r : list;
-  row_cmpx<8>(m, b8); row_cmpx<4>(m, b4); row_cmpx<2>(m, b2); row_cmpx<1>(m, b1);
-  return m;
-}
-
-// partial lists of the splits -> the topn smallest keys per user, ids and scores (the key's score image negated back: negation is
-// exact).  One WAVE per user: the <= MERGE_KEYS keys sit eight per lane, every lane ranks its keys against all of them (keys are
-// distinct: the item id is their low half) and the keys whose rank is below topn are written to their slot.
-constexpr int MERGE_T = 256, MERGE_PER_LANE = MERGE_KEYS / 64;
-__global__ __launch_bounds__(MERGE_T) void dot_topk_merge_kernel(const uint64_t* __restrict__ part, int64_t nq, int nsplit, int topn,
-                                                                 int32_t* __restrict__ top_ids, float* __restrict__ top_scores) {
-  __shared__ uint64_t wk[MERGE_T / 64][MERGE_KEYS];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t b = (int64_t)blockIdx.x * (MERGE_T / 64) + w;
-  if (b >= nq) return;                                                    // (whole waves leave: no workgroup barrier below)
-  const int per = nsplit * topn;
-  const uint64_t* p = part + b * per;
-  uint64_t k[MERGE_PER_LANE];
-  int r[MERGE_PER_LANE];
-  int valid = 0;
-#pragma unroll
-  for (int m = 0; m < MERGE_PER_LANE; ++m) {
-    const int idx = lane + 64 * m;
-    k[m] = idx < per ? p[idx] : PKEY_MAX;
-    r[m] = 0;
-    if (idx < per) wk[w][idx] = k[m];
-    valid += __popcll(__ballot(k[m] != PKEY_MAX));
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  for (int i = 0; i < per; ++i) {
-    const uint64_t o = wk[w][i];
-#pragma unroll
-    for (int m = 0; m < MERGE_PER_LANE; ++m) r[m] += o < k[m] ? 1 : 0;
-  }
-#pragma unroll
-  for (int m = 0; m < MERGE_PER_LANE; ++m) {
-    if (k[m] == PKEY_MAX || r[m] >= topn) continue;
-    top_ids[b * topn + r[m]] = (int32_t)(uint32_t)k[m];
-    if (top_scores) {
-      uint32_t u = (uint32_t)(k[m] >> 32);
-      u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;                     // inverse of the order-preserving image: the negated score
-      top_scores[b * topn + r[m]] = 0.f - __uint_as_float(u);
-    }
-  }
-  if (lane >= valid && lane < topn) {                                     // fewer candidates than topn: pad
-    top_ids[b * topn + lane] = -1;
-    if (top_scores) top_scores[b * topn + lane] = 0.f;
-  }
-}
 
 // The filter lists of a pass as bits, once per pass: bm[b * words + (id >> 5)] bit (id & 31), one wave per user of u_ids.
 __global__ __launch_bounds__(256) void dot_filter_zero_kernel(uint32_t* __restrict__ bm, int64_t n) {
@@ -255,9 +158,7 @@ __global__ __launch_bounds__(256, 2) void dot_pass_kernel(DotArgs a) {
   // (`pend` is replicated over the row's 16 lanes); once a row of a register slot holds 16, that slot's four rows go through the
   // merge network and the n-th keys are renewed
   const int rowbase = 16 * kq;
-  const uint32_t lt_j = (1u << j) - 1u;
-  const int rsh = 16 * (kq & 1);
-  const bool rhi = (kq & 2) != 0;
+  const RowAppend app(kq, j);
   auto flush = [&](bool all) __attribute__((always_inline)) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -267,16 +168,14 @@ __global__ __launch_bounds__(256, 2) void dot_pass_kernel(DotArgs a) {
       if (!__builtin_amdgcn_ballot_w64(all ? n > 0 : n >= 16)) continue;
       const int ur = 4 * kq + reg;
       const uint64_t* row = pbuf + ur * PCAP;
-      uint64_t merged = row_merge16(tk[ur * 16 + j], j < n ? row[j] : PKEY_MAX, j);   // all four rows of the slot at once
-      if (__builtin_amdgcn_ballot_w64(n > 16)) merged = row_merge16(j < topn ? merged : PKEY_MAX, 16 + j < n ? row[16 + j] : PKEY_MAX, j);
-      merged = j < topn ? merged : PKEY_MAX;
+      const uint64_t merged = row_merge_pending(tk[ur * 16 + j], row, n, topn, j);   // all four rows of the slot at once
       tk[ur * 16 + j] = merged;
       pend[reg] = 0;
       const uint32_t nhi = (uint32_t)__shfl((int)(uint32_t)(merged >> 32), rowbase + topn - 1, 64);
       const uint32_t nlo = (uint32_t)__shfl((int)(uint32_t)merged, rowbase + topn - 1, 64);
       if (u0 + ur < a.nq) {                                                           // (rows past the end keep 0 / +inf)
         thr[reg] = ((uint64_t)nhi << 32) | nlo;
-        thrf[reg] = -__uint_as_float((nhi & 0x80000000u) ? (nhi & 0x7fffffffu) : ~nhi);    // inverse of the image, negated back (NaN: list short)
+        thrf[reg] = -topn_key_score(nhi);                                               // negated back (NaN: list short)
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -293,14 +192,12 @@ __global__ __launch_bounds__(256, 2) void dot_pass_kernel(DotArgs a) {
       if (a.item_add) s = __fadd_rn(s, iadd);
       const bool above = s > thrf[reg], maybe = !(s < thrf[reg]) && iok;
       if (!__builtin_amdgcn_ballot_w64(maybe)) continue;                   // most 64-score slots leave here
-      const uint64_t key = pass_key(-s, (uint32_t)item);
+      const uint64_t key = topn_key(s, true, (uint32_t)item);
       bool c = maybe && (above || key < thr[reg]);
       if (c && a.bm) c = ((a.bm[(u0 + ur) * a.bm_words + (item >> 5)] >> (item & 31)) & 1u) == 0u;
       const uint64_t m = __builtin_amdgcn_ballot_w64(c);
       if (m) {
-        const uint32_t rb = ((rhi ? (uint32_t)(m >> 32) : (uint32_t)m) >> rsh) & 0xffffu;   // the candidates of this lane's row
-        if (c) pbuf[ur * PCAP + pend[reg] + __popc(rb & lt_j)] = key;
-        pend[reg] += __popc(rb);
+        app.put(pbuf, ur * PCAP, pend[reg], m, c, [&] { return key; });
         full |= pend[reg] >= 16;
       }
     }
@@ -441,6 +338,7 @@ extern "C" int ktup_eval_dot_topk(const float* U, int64_t ldu, const float* I, i
   else if (nk <= 48) rc = launch_dot_pass<48>(a, blocks, st, name);
   else rc = launch_dot_pass<64>(a, blocks, st, name);
   if (rc) return rc;
-  hipLaunchKernelGGL(dot_topk_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(MERGE_T), 0, st, a.part, nq, a.nsplit, topn, top_ids, top_scores);
+  hipLaunchKernelGGL((topk_merge_kernel<MERGE_PER_LANE, true>), dim3((unsigned)((nq + 3) / 4)), dim3(MERGE_T), 0, st, a.part, nq, a.nsplit, topn, top_ids,
+                     top_scores);
   return check_launch(name);
 }

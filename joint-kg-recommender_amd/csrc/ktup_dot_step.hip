@@ -1,6 +1,6 @@
 // The rec step of the inner-product recommenders (FM fm.py:58-67, coFM cofm.py:99-108, CKE CKE.py:122-135; BPRMF without the
 // options) in ONE launch, and the alignment term of the joint baselines (knowledgable_recommendation.py:385-390) -- see
-// include/ktup_dot_step.h.
+// include/ktup_hip.h.
 //
 // dot_step_kernel: a gather and scatter of at most five rows per example; latency and atomic traffic bound it, not arithmetic.
 // One wave64 owns an example (four examples in flight per workgroup): it reads the user row and the positive and negative
@@ -12,8 +12,7 @@
 
 #include <cstdint>
 
-#include "../ktup_rows.h"
-#include "../../../include/ktup_dot_step.h"
+#include "ktup_rows.h"
 
 using namespace ktup;
 

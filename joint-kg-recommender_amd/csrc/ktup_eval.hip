@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "ktup_pref_geom.h"
+#include "ktup_topn.h"
 
 using namespace ktup;
 
@@ -300,13 +301,6 @@ KTUP_DEV void pair_group_scores(const CF& cf, int nch4, const sptr4 (&qa)[NQ], c
 template <class T>
 KTUP_DEV T uload(const T* p) { return *(const __attribute__((address_space(4))) T*)(uintptr_t)p; }
 
-KTUP_DEV uint64_t count_key(float s, uint32_t id) {    // ktup_rank.hip make_key (ascending)
-  if (s == 0.f) s = 0.f;
-  uint32_t u = __float_as_uint(s);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | id;
-}
-
 template <int MODE, bool L1, bool COUNT = false, bool HYB = false>
 __global__ __launch_bounds__(PairsWG<MODE>::NT) void pairs_kernel(PairsArgs a) {
   static_assert(!HYB || (MODE == 2 && !COUNT), "the hybrid stage is the soft gate's score kernel's");
@@ -424,11 +418,11 @@ __global__ __launch_bounds__(PairsWG<MODE>::NT) void pairs_kernel(PairsArgs a) {
               asm("v_writelane_b32 %0, %1, %2" : "+v"(cntv) : "s"(n), "i"(qi * TH + k));   // (no builtin for it in this compiler)
             }
         } else {
-          const uint64_t key = count_key(sc, cid);
+          const uint64_t key = topn_key(sc, false, cid);
 #pragma unroll
           for (int k = 0; k < TH; ++k)
             if (k < cng[qi]) {
-              const int n = (int)__popcll(__builtin_amdgcn_ballot_w64(key < count_key(__uint_as_float(thb[k]), gid[k])) & inm);
+              const int n = (int)__popcll(__builtin_amdgcn_ballot_w64(key < topn_key(__uint_as_float(thb[k]), false, gid[k])) & inm);
               asm("v_writelane_b32 %0, %1, %2" : "+v"(cntv) : "s"(n), "i"(qi * TH + k));
             }
         }
@@ -438,7 +432,7 @@ __global__ __launch_bounds__(PairsWG<MODE>::NT) void pairs_kernel(PairsArgs a) {
           const uint32_t gid = (uint32_t)uload(a.gold_ids + cg0[qi] + k);
           uint64_t m;
           if (slow || th != th) {
-            m = __builtin_amdgcn_ballot_w64(count_key(sc, cid) < count_key(th, gid));
+            m = __builtin_amdgcn_ballot_w64(topn_key(sc, false, cid) < topn_key(th, false, gid));
           } else {
             const uint64_t lt = __builtin_amdgcn_ballot_w64(sc < th), eq = __builtin_amdgcn_ballot_w64(sc == th);
             m = lt | (eq & __builtin_amdgcn_ballot_w64(cid < gid));
@@ -622,15 +616,7 @@ __global__ __launch_bounds__(HARD_NT) void pairs_hard_kernel(HardArgs a) {
 // one by ballot position -- a few per user and stage once the list has warmed up.  The (users x items) matrix never exists: the
 // batched route wrote and re-read 78 MB per ml1m pass and ran K17 twelve times; what is left is the noise (20 Philox draws and
 // Gumbel transforms per pair) and the d-long distance.  The splits' partial lists are merged by ktup_eval_pass.hip's merge launch.
-constexpr uint64_t SKEY_MAX = ~0ull;
 constexpr int SW_NW = 8, SW_UW = 8;       // waves per workgroup, users per wave (LDS allows two workgroups per CU: 16 waves)
-
-KTUP_DEV uint64_t sweep_key(float s, uint32_t id) {    // ktup_rank.hip make_key, ascending
-  if (s == 0.f) s = 0.f;
-  uint32_t u = __float_as_uint(s);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | id;
-}
 
 struct SweepHardArgs {
   HardArgs h;
@@ -653,8 +639,8 @@ KTUP_DEV SweepState sweep_state_init(char* wb, int topn, int bm_words, int64_t u
   SweepState st;
   st.tk = reinterpret_cast<uint64_t*>(wb); st.thrk = st.tk + UW * topn; st.thrf = reinterpret_cast<float*>(st.thrk + UW);
   st.bm = reinterpret_cast<uint32_t*>(st.thrf + UW); st.topn = topn; st.bm_words = bm_words;
-  for (int idx = lane; idx < UW * topn; idx += 64) st.tk[idx] = SKEY_MAX;
-  if (lane < UW) { st.thrk[lane] = u0 + lane < nq ? SKEY_MAX : 0; st.thrf[lane] = u0 + lane < nq ? __uint_as_float(0x7fffffffu) : -__builtin_inff(); }
+  for (int idx = lane; idx < UW * topn; idx += 64) st.tk[idx] = PKEY_MAX;
+  if (lane < UW) { st.thrk[lane] = u0 + lane < nq ? PKEY_MAX : 0; st.thrf[lane] = u0 + lane < nq ? __uint_as_float(0x7fffffffu) : -__builtin_inff(); }
   for (int idx = lane; idx < UW * bm_words; idx += 64) st.bm[idx] = 0u;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -696,14 +682,14 @@ KTUP_DEV void sweep_rank(const SweepState& st, int r, float acc, int64_t item, b
   bool c = acc < tf;
   const bool tie = !c && !(acc > tf);
   if (__builtin_amdgcn_ballot_w64(tie)) {
-    if (tie) c = sweep_key(acc, (uint32_t)item) < st.thrk[r];
+    if (tie) c = topn_key(acc, false, (uint32_t)item) < st.thrk[r];
   }
   c = c && iok;
   if (c) c = ((st.bm[r * st.bm_words + (lid >> 5)] >> (lid & 31)) & 1u) == 0u;
   uint64_t m = __builtin_amdgcn_ballot_w64(c);
   if (m) {
-    const uint64_t mine = sweep_key(acc, (uint32_t)item);
-    uint64_t list = lane < topn ? st.tk[r * topn + lane] : SKEY_MAX;     // lanes 0..topn-1: the sorted list
+    const uint64_t mine = topn_key(acc, false, (uint32_t)item);
+    uint64_t list = lane < topn ? st.tk[r * topn + lane] : PKEY_MAX;     // lanes 0..topn-1: the sorted list
     while (m) {
       const int src = __builtin_ctzll(m);
       m &= m - 1;
@@ -713,7 +699,7 @@ KTUP_DEV void sweep_rank(const SweepState& st, int r, float acc, int64_t item, b
       if (pos < topn) {
         const uint64_t up = ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(list >> 32), 1, 64) << 32) | (uint32_t)__shfl_up((int)(uint32_t)list, 1, 64);
         list = lane < pos ? list : (lane == pos ? k : up);
-        if (lane >= topn) list = SKEY_MAX;
+        if (lane >= topn) list = PKEY_MAX;
       }
     }
     if (lane < topn) st.tk[r * topn + lane] = list;
@@ -721,7 +707,7 @@ KTUP_DEV void sweep_rank(const SweepState& st, int r, float acc, int64_t item, b
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)list, topn - 1);
     if (lane == 0) {
       st.thrk[r] = ((uint64_t)hi << 32) | lo;
-      st.thrf[r] = __uint_as_float((hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi);   // inverse image; NaN while the list is short
+      st.thrf[r] = topn_key_score(hi);                                            // NaN while the list is short
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

@@ -46,6 +46,7 @@
 #include "ktup_common.h"
 #include "ktup_lane_swap.h"
 #include "ktup_pref_geom.h"
+#include "ktup_topn.h"
 
 namespace ktup {
 namespace {
@@ -67,14 +68,6 @@ struct FGeom {
   // Q [UB][QV][P4] v4 | C [2][IB][P4] v4 | qs [UB][4] | gth [UB][GS] | gkey [UB][GS] u64
   static constexpr size_t LDS = (size_t)(UB * QV + 2 * IB) * P4 * 16 + (size_t)UB * 4 * 4 + (size_t)UB * GS * 4 + (size_t)UB * GS * 8;
 };
-
-KTUP_DEV uint64_t kg_key(float s, bool descending, uint32_t id) {      // = make_key of ktup_rank.hip
-  if (descending) s = -s;
-  if (s == 0.f) s = 0.f;
-  uint32_t u = __float_as_uint(s);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | id;
-}
 
 struct Unc;
 struct FArgs {
@@ -166,7 +159,7 @@ KTUP_DEV void precise_pair(const FArgs& a, int64_t key, int32_t c0, int32_t c1, 
 }
 // is candidate (sc, cid) ordered before gold (sg, gid)?  exact scores first, ids on exact ties; an unordered pair (NaN) -> the keys
 KTUP_DEV bool precise_before(double sc, int32_t cid, double sg, int32_t gid, bool desc, float fsc, float fsg) {
-  if (sc != sc || sg != sg) return kg_key(fsc, desc, (uint32_t)cid) < kg_key(fsg, desc, (uint32_t)gid);
+  if (sc != sc || sg != sg) return topn_key(fsc, desc, (uint32_t)cid) < topn_key(fsg, desc, (uint32_t)gid);
   if (desc) { sc = -sc; sg = -sg; }
   return sc < sg || (sc == sg && (uint32_t)cid < (uint32_t)gid);
 }
@@ -457,7 +450,7 @@ __global__ __launch_bounds__(NW * 64) void kg_count_mc_kernel(FArgs a) {
     if (u0 + row < a.nq) {
       const int64_t g0 = a.gold_off[u0 + row], n = a.gold_off[u0 + row + 1] - g0;
       if (g < n) {
-        k = kg_key(a.gscore[g0 + g], desc, (uint32_t)a.gold_ids[g0 + g]);
+        k = topn_key(a.gscore[g0 + g], desc, (uint32_t)a.gold_ids[g0 + g]);
         th = __uint_as_float(__float_as_uint(a.gscore[g0 + g]) ^ flip);
       }
     }
@@ -584,7 +577,7 @@ __global__ __launch_bounds__(NW * 64) void kg_count_mc_kernel(FArgs a) {
               a.unc[(int64_t)seg * a.unc_cap + slot] = Unc{(int32_t)(u0 + ur), a.gbase + g, (int32_t)cand, __uint_as_float(__float_as_uint(s[reg]) ^ flip)};
             } else {                                             // no window / the segment is full: the keys of the sweep's own scores decide
               if (a.ktol) a.unc_count[a.unc_nseg] = 1;
-              cnt[reg][g] += kg_key(s[reg], false, (uint32_t)cand) < gk ? 1 : 0;      // s is already flipped
+              cnt[reg][g] += topn_key(s[reg], false, (uint32_t)cand) < gk ? 1 : 0;      // s is already flipped
             }
           }
         }
@@ -653,7 +646,7 @@ __global__ __launch_bounds__(256) void kg_unc_resolve_kernel(FArgs a) {
       const int32_t gid = a.gold_ids[gi];
       bool before;
       if (approx) {
-        before = kg_key(u.s, desc, (uint32_t)u.cand) < kg_key(a.gscore[gi], desc, (uint32_t)gid);
+        before = topn_key(u.s, desc, (uint32_t)u.cand) < topn_key(a.gscore[gi], desc, (uint32_t)gid);
       } else {
         double sc, sg;
         precise_pair<16>(a, u.key, u.cand, gid, sub, sc, sg);
@@ -682,16 +675,16 @@ __global__ __launch_bounds__(256) void kg_rank_finalize_kernel(FArgs a, int64_t 
         else for (int64_t f = f0; f < f1 && !filtered; ++f) filtered = a.filt_ids[f] == gid;
       }
       if (filtered) { a.ranks[gi] = -1; a.counts[gi] = -1; continue; }
-      const uint64_t gk = kg_key(a.gscore[gi], desc, (uint32_t)gid);
+      const uint64_t gk = topn_key(a.gscore[gi], desc, (uint32_t)gid);
       const float gs = a.gscore[gi], T = windowed ? a.ktol[key] : 0.f;
       // list entry (score fs, id c) before this gold?  outside the window the float scores decide; inside it the comparison joins the
       // sweep's list (sign -1) and kg_unc_resolve_kernel decides it
       auto before = [&](float fs, int32_t c) {
-        if (!windowed || fs < gs - T || fs > gs + T) return kg_key(fs, desc, (uint32_t)c) < gk;
+        if (!windowed || fs < gs - T || fs > gs + T) return topn_key(fs, desc, (uint32_t)c) < gk;
         const int slot = atomicAdd(a.unc_count + seg, 1);
         if (slot < a.unc_cap) { a.unc[(int64_t)seg * a.unc_cap + slot] = Unc{(int32_t)key, ~(int32_t)gi, c, fs}; return false; }
         a.unc_count[a.unc_nseg] = 1;                           // full: the whole pass falls back to the keys (the resolve step reads this)
-        return kg_key(fs, desc, (uint32_t)c) < gk;
+        return topn_key(fs, desc, (uint32_t)c) < gk;
       };
       int sub = 0;
       if (sorted) {

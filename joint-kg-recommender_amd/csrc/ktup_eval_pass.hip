@@ -34,106 +34,16 @@
 #include "ktup_common.h"
 #include "ktup_lane_swap.h"
 #include "ktup_pref_geom.h"
+#include "ktup_topn.h"
 
 namespace ktup {
 namespace {
 
-constexpr uint64_t PKEY_MAX = ~0ull;
 constexpr int IBT = 16;        // items per LDS tile
-constexpr int TOPN_MAX = 16;   // top-n list capacity per user: one element per lane of a 16-lane row
-constexpr int PCAP = 32;       // pending candidates per user between two merges (a merge is due at 16; one tile adds at most 16)
 // LDS per wave of the sweep: user scalars [16][4] | filter bits [16][bm_words] | pending candidates [16][PCAP] u64 | lists [16][16] u64 |
 // n-th keys [16] u64
 constexpr size_t WAVE_TAIL = (size_t)16 * PCAP * 8 + (size_t)16 * 16 * 8 + (size_t)16 * 8;
 constexpr size_t wave_lds_bytes(int bm_words) { return (((size_t)16 * 4 * 4 + (size_t)16 * bm_words * 4 + 7) & ~(size_t)7) + WAVE_TAIL; }
-
-KTUP_DEV uint64_t pass_key(float s, uint32_t id) {   // ktup_rank.hip make_key, ascending (lower score = better)
-  if (s == 0.f) s = 0.f;
-  uint32_t u = __float_as_uint(s);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | id;
-}
-
-// ---- 16-lane row networks on 64-bit keys (lane j of a row = element j).  Partner j ^ K through DPP: quad_perm for 1 and 2,
-// row_half_mirror . quad_perm[3,2,1,0] for 4 (7 - i then i ^ 3), row_mirror . row_half_mirror for 8.
-template <int K>
-KTUP_DEV uint32_t row_xor32(uint32_t v) {
-  const int x = (int)v;
-  if constexpr (K == 1) return (uint32_t)__builtin_amdgcn_update_dpp(x, x, 0xB1, 0xf, 0xf, false);
-  else if constexpr (K == 2) return (uint32_t)__builtin_amdgcn_update_dpp(x, x, 0x4E, 0xf, 0xf, false);
-  else if constexpr (K == 4) {
-    const int h = __builtin_amdgcn_update_dpp(x, x, 0x141, 0xf, 0xf, false);
-    return (uint32_t)__builtin_amdgcn_update_dpp(h, h, 0x1B, 0xf, 0xf, false);
-  } else {
-    const int m = __builtin_amdgcn_update_dpp(x, x, 0x140, 0xf, 0xf, false);
-    return (uint32_t)__builtin_amdgcn_update_dpp(m, m, 0x141, 0xf, 0xf, false);
-  }
-}
-// compare-exchange with lane j ^ K: keep the smaller key if keep_min, else the larger
-template <int K>
-KTUP_DEV void row_cmpx(uint64_t& v, bool keep_min) {
-  const uint64_t o = ((uint64_t)row_xor32<K>((uint32_t)(v >> 32)) << 32) | row_xor32<K>((uint32_t)v);
-  if ((o < v) == keep_min) v = o;
-}
-KTUP_DEV uint64_t row_mirror64(uint64_t v) {
-  const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_update_dpp(hi, hi, 0x140, 0xf, 0xf, false) << 32) |
-         (uint32_t)__builtin_amdgcn_update_dpp(lo, lo, 0x140, 0xf, 0xf, false);
-}
-// list: a row's ascending 16 keys; cand: up to 16 more in any order (PKEY_MAX = none).  Returns the 16 smallest of the 32, ascending:
-// bitonic sort of the candidates (10 exchanges), elementwise min against their mirror (a bitonic row holding the 16 smallest),
-// bitonic merge (4 exchanges) -- a fixed 14 exchanges instead of one dependent ballot / bpermute round per candidate.
-KTUP_DEV uint64_t row_merge16(uint64_t list, uint64_t cand, int j) {
-  const bool b1 = (j & 1) == 0, b2 = (j & 2) == 0, b4 = (j & 4) == 0, b8 = (j & 8) == 0;
-  row_cmpx<1>(cand, b1 == b2);
-  row_cmpx<2>(cand, b2 == b4); row_cmpx<1>(cand, b1 == b4);
-  row_cmpx<4>(cand, b4 == b8); row_cmpx<2>(cand, b2 == b8); row_cmpx<1>(cand, b1 == b8);
-  row_cmpx<8>(cand, b8); row_cmpx<4>(cand, b4); row_cmpx<2>(cand, b2); row_cmpx<1>(cand, b1);
-  const uint64_t r = row_mirror64(cand);
-  uint64_t m = r < list ? r : list;
-  row_cmpx<8>(m, b8); row_cmpx<4>(m, b4); row_cmpx<2>(m, b2); row_cmpx<1>(m, b1);
-  return m;
-}
-
-// partial lists of the splits -> the topn smallest keys per user.  One WAVE per user: the <= 128 keys sit two per lane, every lane
-// ranks its keys against all of them (keys are distinct: the item id is their low half) and the lanes whose rank is below topn
-// write their key's slot -- no serial k-way merge, no dependent memory round trips (that version: 22 us for 6040 users).
-constexpr int MERGE_T = 256;
-__global__ __launch_bounds__(MERGE_T) void topk_merge_kernel(const uint64_t* __restrict__ part, int64_t nq, int nsplit, int topn,
-                                                             const float* __restrict__ unused, int32_t* __restrict__ top_ids,
-                                                             float* __restrict__ top_scores) {
-  (void)unused;
-  __shared__ uint64_t wk[MERGE_T / 64][128];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t b = (int64_t)blockIdx.x * (MERGE_T / 64) + w;
-  if (b >= nq) return;                                                    // (whole waves leave: no workgroup barrier below)
-  const int per = nsplit * topn;
-  const uint64_t* p = part + b * per;
-  const uint64_t k0 = lane < per ? p[lane] : PKEY_MAX, k1 = 64 + lane < per ? p[64 + lane] : PKEY_MAX;
-  wk[w][lane] = k0; wk[w][64 + lane] = k1;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  int r0 = 0, r1 = 0;
-  for (int i = 0; i < per; ++i) {
-    const uint64_t k = wk[w][i];
-    r0 += k < k0; r1 += k < k1;
-  }
-  const int valid = __popcll(__ballot(k0 != PKEY_MAX)) + __popcll(__ballot(k1 != PKEY_MAX));
-  auto put = [&](uint64_t key, int r) {
-    if (key == PKEY_MAX || r >= topn) return;
-    top_ids[b * topn + r] = (int32_t)(uint32_t)key;
-    if (top_scores) {
-      uint32_t u = (uint32_t)(key >> 32);
-      u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;                     // inverse of the order-preserving image
-      top_scores[b * topn + r] = __uint_as_float(u);
-    }
-  };
-  put(k0, r0); put(k1, r1);
-  if (lane >= valid && lane < topn) {                                     // fewer candidates than topn: pad
-    top_ids[b * topn + lane] = -1;
-    if (top_scores) top_scores[b * topn + lane] = 0.f;
-  }
-}
 
 // The filter lists of a pass as bits, built ONCE per pass instead of once per catalogue split inside the sweep (where the walk was 15 of
 // the sweep's 180 us: every split's workgroup of a user block repeated it, latency-bound, before its first tile): one wave per 16
@@ -402,9 +312,7 @@ __global__ __launch_bounds__(256, G::MINW) void eval_pass_q_kernel(QArgs a) {
   int pend[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int reg = 0; reg < 4; ++reg) thrf[reg] = u0 + 4 * kq + reg < a.nq ? __uint_as_float(0x7fffffffu) : -__builtin_inff();
-  const uint32_t lt_j = (1u << j) - 1u;
-  const int rsh = 16 * (kq & 1);
-  const bool rhi = (kq & 2) != 0;
+  const RowAppend app(kq, j);
   auto flush = [&](bool all) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -414,14 +322,12 @@ __global__ __launch_bounds__(256, G::MINW) void eval_pass_q_kernel(QArgs a) {
       if (!__builtin_amdgcn_ballot_w64(all ? n > 0 : n >= 16)) continue;
       const int ur = 4 * kq + reg;
       const uint64_t* row = pbuf + ur * PCAP;
-      uint64_t merged = row_merge16(tk[ur * 16 + j], j < n ? row[j] : PKEY_MAX, j);   // all four rows of the slot at once
-      if (__builtin_amdgcn_ballot_w64(n > 16)) merged = row_merge16(j < topn ? merged : PKEY_MAX, 16 + j < n ? row[16 + j] : PKEY_MAX, j);
-      merged = j < topn ? merged : PKEY_MAX;
+      const uint64_t merged = row_merge_pending(tk[ur * 16 + j], row, n, topn, j);   // all four rows of the slot at once
       tk[ur * 16 + j] = merged;
       pend[reg] = 0;
       if (u0 + ur < a.nq) {                                                       // (rows past the end keep thrf = -inf, thrk = 0)
         const uint32_t hi = (uint32_t)__shfl((int)(merged >> 32), rowbase + topn - 1, 64);
-        const float own = __uint_as_float((hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi);   // inverse of the order-preserving image (NaN: list short)
+        const float own = topn_key_score(hi);                                     // (NaN: list short)
         thrf[reg] = own;                                                          // (the next tile's refresh brings the shared bound back)
         if (j == topn - 1) {
           thrk[ur] = merged;
@@ -505,15 +411,13 @@ __global__ __launch_bounds__(256, G::MINW) void eval_pass_q_kernel(QArgs a) {
       if (m_ngt == 0) continue;
       bool c = score < thrf[reg];
       if (m_ngt != __builtin_amdgcn_ballot_w64(c)) {                       // the keys decide (always while the list is short)
-        if (!c && !(score > thrf[reg])) c = pass_key(score, (uint32_t)item) < thrk[ur];
+        if (!c && !(score > thrf[reg])) c = topn_key(score, false, (uint32_t)item) < thrk[ur];
       }
       c = c && iok;
       if (c) c = ((bm[ur * a.bm_words + (lid >> 5)] >> (lid & 31)) & 1u) == 0u;
       const uint64_t m = __builtin_amdgcn_ballot_w64(c);
       if (m) {
-        const uint32_t rb = ((rhi ? (uint32_t)(m >> 32) : (uint32_t)m) >> rsh) & 0xffffu;   // the candidates of this lane's row
-        if (c) pbuf[ur * PCAP + pend[reg] + __popc(rb & lt_j)] = pass_key(score, (uint32_t)item);
-        pend[reg] += __popc(rb);
+        app.put(pbuf, ur * PCAP, pend[reg], m, c, [&] { return topn_key(score, false, (uint32_t)item); });
         full |= pend[reg] >= 16;
       }
     }
@@ -998,7 +902,7 @@ int launch_q(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, cons
   (void)hipFuncSetAttribute((const void*)eval_pass_q_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL((eval_pass_q_kernel<G>), dim3((unsigned)ublocks, (unsigned)nsplit), dim3(256), lds, st, a);
   if (int e = check_launch(name)) return e;
-  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(MERGE_T), 0, st, q.part, nq, nsplit, topn, (const float*)nullptr, top_ids,
+  hipLaunchKernelGGL((topk_merge_kernel<2, false>), dim3((unsigned)((nq + 3) / 4)), dim3(MERGE_T), 0, st, q.part, nq, nsplit, topn, top_ids,
                      top_scores);
   return check_launch(name);
 }
@@ -1023,7 +927,7 @@ namespace ktup {
 
 // the merge of the splits' partial lists, for the other sweeps (ktup_eval.hip: the hard gate's pass)
 int launch_topk_merge(const uint64_t* part, int64_t nq, int nsplit, int topn, int32_t* top_ids, float* top_scores, hipStream_t st, const char* name) {
-  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(MERGE_T), 0, st, part, nq, nsplit, topn, (const float*)nullptr, top_ids,
+  hipLaunchKernelGGL((topk_merge_kernel<2, false>), dim3((unsigned)((nq + 3) / 4)), dim3(MERGE_T), 0, st, part, nq, nsplit, topn, top_ids,
                      top_scores);
   return check_launch(name);
 }

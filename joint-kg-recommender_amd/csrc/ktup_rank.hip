@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "ktup_common.h"
+#include "ktup_topn.h"
 
 using namespace ktup;
 
@@ -22,14 +23,6 @@ namespace {
 
 constexpr uint64_t KEY_MAX = ~0ull;
 constexpr int64_t MAX_LDS_CAND = 19000;  // 152 KB of keys + reduction scratch within the 160 KB LDS
-
-KTUP_DEV uint64_t make_key(float s, bool descending, uint32_t id) {
-  if (descending) s = -s;
-  if (s == 0.f) s = 0.f;  // -0.0 and +0.0 compare equal in the reference's sort: one key for both
-  uint32_t u = __float_as_uint(s);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | id;
-}
 
 KTUP_DEV uint64_t wave_min64(uint64_t v) {
 #pragma unroll
@@ -47,7 +40,7 @@ KTUP_DEV int wave_sum_int(int v) {
 }
 
 KTUP_DEV void load_keys(uint64_t* keys, const float* row, int64_t n_cand, bool descending, const int32_t* fids, int64_t nf) {
-  for (int64_t j = threadIdx.x; j < n_cand; j += 256) keys[j] = make_key(row[j], descending, (uint32_t)j);
+  for (int64_t j = threadIdx.x; j < n_cand; j += 256) keys[j] = topn_key(row[j], descending, (uint32_t)j);
   __syncthreads();
   for (int64_t f = threadIdx.x; f < nf; f += 256) {
     const int32_t id = fids[f];
@@ -143,7 +136,7 @@ __global__ __launch_bounds__(256) void gold_ranks_stream_kernel(const float* __r
       uint64_t k = KEY_MAX;
       if (gi < g1) {
         const int32_t g = gold_ids[gi];
-        if (g >= 0 && g < n_cand && !((filt[g >> 5] >> (g & 31)) & 1u)) k = make_key(row[g], desc, (uint32_t)g);
+        if (g >= 0 && g < n_cand && !((filt[g >> 5] >> (g & 31)) & 1u)) k = topn_key(row[g], desc, (uint32_t)g);
       }
       gkeys[threadIdx.x] = k;
     }
@@ -163,7 +156,7 @@ __global__ __launch_bounds__(256) void gold_ranks_stream_kernel(const float* __r
       for (int u = 0; u < STREAM_U; ++u) {
         const int64_t j = j0 + 256 * u;
         const bool on = j < n_cand && !((skip[(j < n_cand ? j : 0) >> 5] >> (j & 31)) & 1u);
-        const uint64_t k = on ? make_key(v[u], desc, (uint32_t)j) : KEY_MAX;     // KEY_MAX is below no gold key
+        const uint64_t k = on ? topn_key(v[u], desc, (uint32_t)j) : KEY_MAX;     // KEY_MAX is below no gold key
 #pragma unroll
         for (int i = 0; i < GOLD_B; ++i) cnt[i] += k < gk[i] ? 1 : 0;
       }
@@ -195,7 +188,7 @@ KTUP_DEV bool load_chunk(uint64_t* keys, const float* row, int64_t c0, int len, 
                          const int32_t* fids, int64_t nf) {
   int any = 0;
   for (int j = threadIdx.x; j < len; j += 256) {
-    uint64_t k = make_key(row[c0 + j], descending, (uint32_t)(c0 + j));
+    uint64_t k = topn_key(row[c0 + j], descending, (uint32_t)(c0 + j));
     if (k >= limit) k = KEY_MAX;
     any |= k != KEY_MAX;
     keys[j] = k;
@@ -284,7 +277,7 @@ __global__ __launch_bounds__(256) void gold_ranks_chunked_kernel(const float* __
       const int32_t g = gold_ids[gb + i];
       const bool ok = g >= 0 && g < n_cand;
       gid[i] = ok ? g : -1;
-      gkey[i] = ok ? make_key(row[g], descending != 0, (uint32_t)g) : KEY_MAX;
+      gkey[i] = ok ? topn_key(row[g], descending != 0, (uint32_t)g) : KEY_MAX;
       acc[i] = 0;
     }
     __syncthreads();
@@ -495,7 +488,7 @@ __global__ __launch_bounds__(256) void gold_rank_counts_kernel(const float* __re
     __syncthreads();
     // local candidate j has the global id c_lo + c_stride * j (c_stride = 1: a contiguous block; = world: rows g % world == rank of a
     // row-sharded table); a listed id lies in this shard when it is on that lattice
-    for (int j = threadIdx.x; j < len; j += 256) keys[j] = make_key(row[c0 + j], descending != 0, (uint32_t)(c_lo + c_stride * (c0 + j)));
+    for (int j = threadIdx.x; j < len; j += 256) keys[j] = topn_key(row[c0 + j], descending != 0, (uint32_t)(c_lo + c_stride * (c0 + j)));
     __syncthreads();
     for (int64_t f = threadIdx.x; f < nf; f += 256) {                  // filtered candidates and the golds themselves do not count
       const int64_t off = (int64_t)fids[f] - c_lo;
@@ -509,7 +502,7 @@ __global__ __launch_bounds__(256) void gold_rank_counts_kernel(const float* __re
     }
     __syncthreads();
     for (int64_t gi = g0; gi < g1; ++gi) {
-      const uint64_t gk = make_key(gold_scores[gi], descending != 0, (uint32_t)gold_ids[gi]);
+      const uint64_t gk = topn_key(gold_scores[gi], descending != 0, (uint32_t)gold_ids[gi]);
       int cnt = 0;
       for (int j = threadIdx.x; j < len; j += 256) cnt += keys[j] < gk ? 1 : 0;
       cnt = wave_sum_int(cnt);

@@ -23,10 +23,9 @@
 
 #include <cstdint>
 
-#include "../ktup_common.h"
-#include "../ktup_lane_swap.h"
-#include "../ktup_pref_geom.h"
-#include "../../../include/ktup_transd.h"
+#include "ktup_common.h"
+#include "ktup_lane_swap.h"
+#include "ktup_pref_geom.h"
 
 using namespace ktup;
 

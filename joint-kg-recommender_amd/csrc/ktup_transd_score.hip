@@ -7,8 +7,7 @@
 // Backward, with g = gscore * dist'(v) and gamma = g . r_p:
 //   dh = g + gamma h_p    dh_p = gamma h    dt = -g - gamma t_p    dt_p = -gamma t    dr = g    dr_p = (alpha - beta) g
 // added into the caller's buffers with float atomics.
-#include "../ktup_rows.h"
-#include "../../../include/ktup_transd.h"
+#include "ktup_rows.h"
 
 using namespace ktup;
 

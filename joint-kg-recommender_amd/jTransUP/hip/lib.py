@@ -152,6 +152,18 @@ SIGNATURES = {
     'ktup_negsample_kg': [c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_l, c_u, c_u, c_p, c_p, c_p, c_p],
     'ktup_feed_rec': [c_p, c_p, c_l, c_l, c_p, c_p, c_l, c_p, c_l, c_u, c_i, c_p, c_p, c_p, c_p, c_p],
     'ktup_feed_kg': [c_p, c_p, c_p, c_l, c_l, c_p, c_p, c_l, c_l, c_p, c_l, c_u, c_p, c_p, c_p, c_p, c_p],
+    'ktup_score_transd_fwd': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_p, c_p],
+    'ktup_score_transd_bwd': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    'ktup_eval_transd_workspace_bytes': [c_i, c_l],
+    'ktup_eval_transd_scores': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_l, c_i, c_i, c_p, c_l, c_p, c_p],
+    'ktup_eval_kg_ranks_transd_workspace_bytes': [c_i, c_l, c_l],
+    'ktup_eval_kg_ranks_transd': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
+                                  c_p, c_l, c_p, c_p],
+    'ktup_eval_dot_topk_workspace_bytes': [c_i, c_l, c_l, c_i, c_i],
+    'ktup_eval_dot_topk': [c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
+    'ktup_train_dot_step_supported': [c_i],
+    'ktup_train_dot_step': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_i, c_p, c_p, c_l, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p],
+    'ktup_reg_align_pairs': [c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_l, c_i, c_f, c_p, c_p, c_p, c_p],
 }
 _RESTYPE = {'ktup_last_error': ctypes.c_char_p, 'ktup_shard_reduce_list_len': ctypes.c_int64, 'ktup_shard_route_workspace_bytes': ctypes.c_size_t,
             'ktup_shard_route_sort_bytes': ctypes.c_size_t, 'ktup_pref_workspace_bytes': ctypes.c_size_t, 'ktup_eval_kg_ranks_workspace_bytes': ctypes.c_size_t, 'ktup_eval_kg_ranks_transr_workspace_bytes': ctypes.c_size_t, 'ktup_eval_kg_ranks_fused_workspace_bytes': ctypes.c_size_t,
@@ -160,34 +172,8 @@ _RESTYPE = {'ktup_last_error': ctypes.c_char_p, 'ktup_shard_reduce_list_len': ct
             'ktup_score_pref_bwd_workspace_bytes': ctypes.c_size_t, 'ktup_segment_workspace_bytes': ctypes.c_size_t, 'ktup_shard_dedupe_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_pref_topk_workspace_bytes': ctypes.c_size_t, 'ktup_eval_pref_topk_hard_workspace_bytes': ctypes.c_size_t,
             'ktup_score_kg_bwd_workspace_bytes': ctypes.c_size_t, 'ktup_score_bprmf_bwd_workspace_bytes': ctypes.c_size_t,
-            'ktup_train_rec_step_rows_ws_bytes': ctypes.c_size_t}
-
-# The TransD extension of the ABI (include/ktup_transd.h; kernels under csrc/transd/, same library).  A table of its own: SIGNATURES
-# mirrors ktup_hip.h symbol for symbol; the two are to be merged together with the two headers.
-SIGNATURES_TRANSD = {
-    'ktup_score_transd_fwd': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_p, c_p],
-    'ktup_score_transd_bwd': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
-    'ktup_eval_transd_workspace_bytes': [c_i, c_l],
-    'ktup_eval_transd_scores': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_l, c_i, c_i, c_p, c_l, c_p, c_p],
-    'ktup_eval_kg_ranks_transd_workspace_bytes': [c_i, c_l, c_l],
-    'ktup_eval_kg_ranks_transd': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p,
-                                  c_p, c_l, c_p, c_p],
-}
-_RESTYPE.update({'ktup_eval_transd_workspace_bytes': ctypes.c_size_t, 'ktup_eval_kg_ranks_transd_workspace_bytes': ctypes.c_size_t})
-
-# The inner-product evaluation pass (include/ktup_dot.h; kernels under csrc/dot/, same library): a table of its own for the same reason.
-SIGNATURES_DOT = {
-    'ktup_eval_dot_topk_workspace_bytes': [c_i, c_l, c_l, c_i, c_i],
-    'ktup_eval_dot_topk': [c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
-}
-_RESTYPE.update({'ktup_eval_dot_topk_workspace_bytes': ctypes.c_size_t})
-
-# The training step of the inner-product recommenders (include/ktup_dot_step.h; kernels under csrc/dotstep/, same library).
-SIGNATURES_DOT_STEP = {
-    'ktup_train_dot_step_supported': [c_i],
-    'ktup_train_dot_step': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_i, c_p, c_p, c_l, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p],
-    'ktup_reg_align_pairs': [c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_l, c_i, c_f, c_p, c_p, c_p, c_p],
-}
+            'ktup_train_rec_step_rows_ws_bytes': ctypes.c_size_t, 'ktup_eval_transd_workspace_bytes': ctypes.c_size_t,
+            'ktup_eval_kg_ranks_transd_workspace_bytes': ctypes.c_size_t, 'ktup_eval_dot_topk_workspace_bytes': ctypes.c_size_t}
 
 _lib = None
 
@@ -208,8 +194,7 @@ def load():
         raise KtupError('libktup_hip.so not found at %s -- build it with '
                         '`python joint-kg-recommender_amd/build_hip.py` (there is no CPU fallback)' % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_TRANSD.items()) + list(SIGNATURES_DOT.items()) \
-            + list(SIGNATURES_DOT_STEP.items()):
+    for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, ctypes.c_int)

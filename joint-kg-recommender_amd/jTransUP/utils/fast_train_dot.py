@@ -3,7 +3,7 @@ baselines coFM and CKE (knowledgable_recommendation.py:330-401 -> BaselineJointS
 (flat gradient bucket, data-parallel slice + all-reduce, pre-bound launches, HIP-graph replay, the K20 clip + step).
 
 Their rec step is one computation -- the inner product of a user row with an item-side row, optional bias terms, the BPR loss, the
-gradients back into the gathered rows -- and ONE launch: ktup_train_dot_step (include/ktup_dot_step.h), followed by
+gradients back into the gathered rows -- and ONE launch: ktup_train_dot_step (include/ktup_hip.h), followed by
 ktup_optim_clip_step.  The kg side takes what exists: ktup_train_kg_step (TransE) for coFM, the TransR launches of KGStepper for
 CKE.  coFM with its own item table adds the alignment term of knowledgable_recommendation.py:385-390 to EVERY step:
 ktup_reg_align_pairs, whose id lists the host builds exactly as the autograd route does (getMappedEntities / getMappedItems on the

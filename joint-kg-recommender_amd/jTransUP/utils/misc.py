@@ -35,7 +35,7 @@ def projection_transR_pytorch_batch(original, proj_matrix):
 
 def projection_transD_pytorch_samesize(entity_embedding, entity_projection, relation_projection):
     """utils/misc.py:36-37: e + (e . e_p) r_p.  The torch statement of TransD's projection, kept with the reference's name; the model
-    (models/transD.py) runs it inside the HIP kernels of csrc/transd/."""
+    (models/transD.py) runs it inside the HIP kernels of csrc/ktup_transd_*.hip."""
     return entity_embedding + torch.sum(entity_embedding * entity_projection, dim=entity_embedding.dim() - 1, keepdim=True) * relation_projection
 
 

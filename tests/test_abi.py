@@ -45,6 +45,37 @@ def test_binding_table_matches_header(lib):
     assert lib.load().ktup_version() >= 1
 
 
+# the entry points that were added as separate "extensions" of the ABI (TransD, the inner-product evaluation pass and training step)
+ONCE_SEPARATE = ['ktup_eval_kg_ranks_transd', 'ktup_eval_kg_ranks_transd_workspace_bytes', 'ktup_eval_transd_scores',
+                 'ktup_eval_transd_workspace_bytes', 'ktup_score_transd_bwd', 'ktup_score_transd_fwd',
+                 'ktup_eval_dot_topk', 'ktup_eval_dot_topk_workspace_bytes',
+                 'ktup_reg_align_pairs', 'ktup_train_dot_step', 'ktup_train_dot_step_supported']
+
+
+def test_header_library_and_binding_table_agree(lib):
+    """One header, one table, one library: the same symbols, argument counts and return types in all three."""
+    syms = declared_symbols()
+    assert not set(ONCE_SEPARATE) - set(syms)
+    handle = ctypes.CDLL(lib.LIB_PATH)
+    missing = [s for s in syms if not hasattr(handle, s)]
+    assert not missing, 'declared in include/ktup_hip.h but not exported: %s' % missing
+    assert sorted(lib.SIGNATURES) == syms
+    assert not set(lib._RESTYPE) - set(syms)
+    loaded = lib.load()
+    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
+    for s in syms:
+        fn = getattr(loaded, s)
+        assert fn.argtypes == lib.SIGNATURES[s], s
+        assert fn.restype is lib._RESTYPE.get(s, ctypes.c_int), s
+        ret, args = re.search(r'\b(\w+)[\s*]+%s\s*\(([^)]*)\)' % s, text).groups()      # (the type's last word: `const char*` -> char)
+        nargs = 0 if args.strip() in ('', 'void') else len(args.split(','))
+        assert nargs == len(lib.SIGNATURES[s]), s
+        if s in lib._RESTYPE and s not in ('ktup_last_error', 'ktup_shard_reduce_list_len'):
+            assert lib._RESTYPE[s] is ctypes.c_size_t and ret == 'size_t', s
+        elif s not in lib._RESTYPE:
+            assert ret == 'int', s
+
+
 def test_invalid_argument_is_reported_not_swallowed(lib):
     # argument validation happens on the host before any launch, so this is safe without a GPU
     with pytest.raises(lib.KtupError) as e:

@@ -1,22 +1,13 @@
-"""The inner-product evaluation pass without a GPU: the extension header against the built library and the binding table, the
-models' and the driver's surface, and host-side argument validation of the new entry point (no launch is made)."""
+"""The inner-product evaluation pass without a GPU: the workspace size, the models' and the driver's surface, and host-side
+argument validation of the entry point (no launch is made)."""
 import ctypes
 import inspect
 import os
-import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, 'include', 'ktup_hip.h')
-HEADER_DOT = os.path.join(ROOT, 'include', 'ktup_dot.h')
 ERR_INVALID, ERR_UNSUPPORTED = -1, -3
-
-
-def declared_symbols(path):
-    text = open(path).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(ktup_[a-z0-9_]+)\s*\(', text)))
 
 
 @pytest.fixture(scope='module')
@@ -31,18 +22,8 @@ def lib():
     return L
 
 
-def test_extension_header_library_and_binding_table_agree(lib):
-    syms = declared_symbols(HEADER_DOT)
-    assert syms == ['ktup_eval_dot_topk', 'ktup_eval_dot_topk_workspace_bytes']
-    handle = ctypes.CDLL(lib.LIB_PATH)
-    missing = [s for s in syms if not hasattr(handle, s)]
-    assert not missing, 'declared in include/ktup_dot.h but not exported: %s' % missing
-    assert sorted(lib.SIGNATURES_DOT) == syms
-    assert sorted(lib.SIGNATURES) == declared_symbols(HEADER)            # the first table still mirrors the first header
-    assert not set(lib.SIGNATURES) & set(lib.SIGNATURES_DOT) and not set(lib.SIGNATURES_TRANSD) & set(lib.SIGNATURES_DOT)
+def test_workspace_sizes(lib):
     loaded = lib.load()
-    for s in syms:
-        assert getattr(loaded, s).argtypes == lib.SIGNATURES_DOT[s]
     assert loaded.ktup_eval_dot_topk_workspace_bytes.restype is ctypes.c_size_t
     # the partial lists of the splits (8 bytes a key) and one filter bit per (user, item)
     one = loaded.ktup_eval_dot_topk_workspace_bytes(64, 100, 3240, 10, 1)

@@ -58,6 +58,21 @@ def filters(rng, nq, ni, mean):
     return torch.from_numpy(off).to(DEV), torch.from_numpy(flat).to(DEV)
 
 
+def filters_all_but_two(rng, nq, ni):
+    """As filters(), but query 1 keeps exactly two items (one in the first tile, one in the catalogue's short last tile): its list
+    ends in -1 / 0.f padding whatever the number of splits."""
+    off, flat = filters(rng, nq, ni, max(2, ni // 8))
+    off, flat = off.cpu().numpy(), flat.cpu().numpy()
+    keep = np.setdiff1d(np.arange(ni, dtype=np.int32), [7, ni - 2])
+    flat = np.concatenate([flat[:off[1]], keep, flat[off[2]:]]).astype(np.int32)
+    off[2:] -= ni - keep.size
+    return torch.from_numpy(off).to(DEV), torch.from_numpy(flat).to(DEV)
+
+
+# 70 users: two user blocks, the second with a ragged last wave; 531 items: 33 whole 16-item tiles and a short one -- splits are whole
+# tiles, so a request for 17 or for 32 gets 17 splits of 32 items (272 keys at topn 16); 499 items: 32 splits of one tile each (the
+# last one short) -- with topn 16 the merge kernel's full 512 keys
+MANY_SPLITS = [(12, 70, 531, 70, 16), (12, 70, 531, 70, 3), (12, 70, 499, 70, 16)]
 SHAPES = [(64, 300, 177, 65, 16), (100, 70, 5, 63, 10), (37, 90, 33, 1, 3), (50, 500, 1000, 129, 1), (20, 64, 45, 33, 10),
           (256, 40, 130, 17, 10), (8, 50, 40000, 33, 10), (64, 6040, 3240, 6040, 10)]
 _CASES = {}
@@ -79,7 +94,7 @@ def case(shape):
     scale = 0.25 * d ** 0.5                                               # the spread of the dot products: the terms reorder the lists
     ua = (torch.randn(nq, generator=gen) * scale).to(DEV)
     ia = (torch.randn(ni, generator=gen) * scale).to(DEV)
-    f_off, f_ids = filters(rng, nq, ni, min(165, max(2, ni // 8)))
+    f_off, f_ids = filters_all_but_two(rng, nq, ni) if shape in MANY_SPLITS else filters(rng, nq, ni, min(165, max(2, ni // 8)))
     want = {}
     for terms in (False, True):
         for filt in (False, True):
@@ -112,12 +127,17 @@ def test_pass_is_the_matrix_route_bit_for_bit(shape, terms, filt):
     assert torch.equal(only, w_ids)                                       # top_scores == NULL
 
 
-@pytest.mark.parametrize('nsplit', [0, 1, 3, 8])
-@pytest.mark.parametrize('shape', [SHAPES[0], SHAPES[6]])
+@pytest.mark.parametrize('nsplit', [0, 1, 3, 8, 17, 32])
+@pytest.mark.parametrize('shape', [SHAPES[0], SHAPES[6]] + MANY_SPLITS)
 def test_any_number_of_catalogue_splits(shape, nsplit):
+    """More than 8 splits of topn 16 are more than 128 keys per user: only here does the merge kernel hold over two keys per lane."""
     U, I, u, ua, ia, f_off, f_ids, want = case(shape)
     got = ops().eval_dot_topk(U, I, u, shape[4], f_off, f_ids, ua, ia, with_scores=True, nsplit=nsplit)
     assert torch.equal(got[0], want[True, True][0]) and torch.equal(got[1], want[True, True][1])
+    if shape in MANY_SPLITS:
+        assert got[0][1].tolist()[2:] == [-1] * (shape[4] - 2) and sorted(got[0][1].tolist()[:2]) == [7, shape[2] - 2]
+        assert got[1][1].tolist()[2:] == [0.0] * (shape[4] - 2)           # the padding of a list that ends short
+        assert int(f_off[3] - f_off[2]) == 0 and bool((got[0][2] >= 0).all())   # query 2: nothing filtered
 
 
 def test_user_table_with_a_pitch_and_unaligned_item_rows():

@@ -1,4 +1,4 @@
-"""GPU parity of ktup_train_dot_step and ktup_reg_align_pairs (include/ktup_dot_step.h) through the C ABI: the kernels against fp64
+"""GPU parity of ktup_train_dot_step and ktup_reg_align_pairs (include/ktup_hip.h) through the C ABI: the kernels against fp64
 torch on the CPU from the same fp32 inputs.  The tables are small so that rows collide: 7 users, 11 items, 6 rows of the second
 item-side table of which the last is the pad row.
 

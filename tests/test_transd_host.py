@@ -1,12 +1,10 @@
-"""TransD without a GPU: the model factory and class surface, the extension header against the built library and the binding table,
-host-side argument validation of the new entry points, and the fixtures against their generator."""
-import ctypes
+"""TransD without a GPU: the model factory and class surface, the workspace sizes, host-side argument validation of the entry
+points, and the fixtures against their generator."""
 import filecmp
 import inspect
 import json
 import logging
 import os
-import re
 import subprocess
 import sys
 import types
@@ -16,16 +14,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden')
-HEADER = os.path.join(ROOT, 'include', 'ktup_hip.h')
-HEADER_TRANSD = os.path.join(ROOT, 'include', 'ktup_transd.h')
 # a checkout of the reference (TaoMiner/joint-kg-recommender): where the build container keeps it, or wherever the variable says
 REFERENCE = os.environ.get('KTUP_REFERENCE_CHECKOUT', '/root/reference')
-
-
-def declared_symbols(path):
-    text = open(path).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(ktup_[a-z0-9_]+)\s*\(', text)))
 
 
 @pytest.fixture(scope='module')
@@ -86,18 +76,8 @@ def test_class_surface_covers_the_reference():
         assert callable(getattr(transD.TransDModel, extra))
 
 
-def test_extension_header_library_and_binding_table_agree(lib):
-    syms = declared_symbols(HEADER_TRANSD)
-    assert len(syms) == 6 and all('transd' in s for s in syms), syms
-    handle = ctypes.CDLL(lib.LIB_PATH)
-    missing = [s for s in syms if not hasattr(handle, s)]
-    assert not missing, 'declared in include/ktup_transd.h but not exported: %s' % missing
-    assert sorted(lib.SIGNATURES_TRANSD) == syms
-    assert sorted(lib.SIGNATURES) == declared_symbols(HEADER)            # the first table still mirrors the first header
-    assert not set(lib.SIGNATURES) & set(lib.SIGNATURES_TRANSD)
+def test_workspace_sizes(lib):
     loaded = lib.load()
-    for s in syms:
-        assert getattr(loaded, s).argtypes == lib.SIGNATURES_TRANSD[s]
     assert loaded.ktup_eval_transd_workspace_bytes(100, 512) == (512 * 3 * 100 + 512 * 4) * 4
     assert loaded.ktup_eval_transd_workspace_bytes(50, 8) == (8 * 3 * 52 + 8 * 4) * 4      # rows padded to whole 16-byte chunks
     assert loaded.ktup_eval_transd_workspace_bytes(0, 8) == 0
