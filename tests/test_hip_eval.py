@@ -12,6 +12,7 @@ import torch
 
 from oracle import cpu_ref as O
 from jTransUP.hip import lib as L
+from tests.philox_host import _host_philox_uniforms
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
@@ -243,24 +244,6 @@ def test_hard_gate_pass_in_one_sweep(l1, noise):
         assert got[0][1].tolist() == [-1] * topn
         nf = G.eval_pref_topk_hard(U, u, items, l1, topn, mode, uni, seed, off)
         assert torch.equal(nf, G.topk_filtered(mat, False, topn))
-
-
-def _host_philox_uniforms(seed, first, count):
-    """u01 of the library's Philox4x32-10 stream (csrc/ktup_common.h: counter = (block, 0x4b545550), key = seed; draw i is word i & 3 of
-    block i >> 2; 24-bit lattice) at positions first .. first + count - 1, in numpy."""
-    idx = np.arange(first, first + count, dtype=np.uint64)
-    blk = idx >> np.uint64(2)
-    c = [(blk & np.uint64(0xffffffff)).astype(np.uint64), (blk >> np.uint64(32)).astype(np.uint64),
-         np.full(count, 0x4b545550, np.uint64), np.zeros(count, np.uint64)]
-    a, b = np.uint64(seed & 0xffffffff), np.uint64((seed >> 32) & 0xffffffff)
-    M = np.uint64(0xffffffff)
-    for _ in range(10):
-        m0, m1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
-        hi0, lo0, hi1, lo1 = m0 >> np.uint64(32), m0 & M, m1 >> np.uint64(32), m1 & M
-        c = [(hi1 ^ c[1] ^ a) & M, lo1, (hi0 ^ c[3] ^ b) & M, lo0]
-        a, b = (a + np.uint64(0x9E3779B9)) & M, (b + np.uint64(0xBB67AE85)) & M
-    words = np.stack(c, axis=1)[np.arange(count), (idx & np.uint64(3)).astype(np.int64)]
-    return ((words >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)
 
 
 @pytest.mark.gpu
