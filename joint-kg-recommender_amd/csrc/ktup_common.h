@@ -29,6 +29,7 @@ int opt_deterministic();
 int opt_fwd_wide();
 int opt_fwd_split();
 int opt_fwd_buf_gather();
+int opt_fwd_split_pack();
 hipStream_t fork_side(hipStream_t st);              // ktup_runtime.hip: second stream for input-only work (nullptr: stay on st)
 void join_side(hipStream_t st, hipStream_t side);
 

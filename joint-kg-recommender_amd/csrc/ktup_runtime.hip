@@ -59,6 +59,8 @@ Option g_opts[] = {
                                                                             // on v_mfma_f32_16x16x32_bf16 where the geometry allows: ktup_score_pref_mc.hip)
     {"fwd_buf_gather", "KTUP_FWD_BUF_GATHER", {env_int("KTUP_FWD_BUF_GATHER", 1)}},   // 0: K5-K7 soft-gate forward at d <= 128 gathers its rows through 64-bit pointers (1: row byte offsets formed once
                                                                             // per id, buffer loads at 32-bit offsets, per-tile fall-back for rows past 4 GB: ktup_score_pref_mc.hip)
+    {"fwd_split_pack", "KTUP_FWD_SPLIT_PACK", {env_int("KTUP_FWD_SPLIT_PACK", 1)}},   // 0: the split stage 2 (fwd_split) issues its six products as six MFMAs per tile and table for every P (1: at P <= 20
+                                                                            // packed into four, at P <= 16 three, by ktup_split_plan.h)
 };
 Option* find(const char* name) {
   for (auto& o : g_opts)
@@ -84,6 +86,7 @@ int opt_fwd_wide() { return g_opts[14].value.load(std::memory_order_relaxed); }
 int opt_deterministic() { return g_opts[15].value.load(std::memory_order_relaxed); }
 int opt_fwd_split() { return g_opts[16].value.load(std::memory_order_relaxed); }
 int opt_fwd_buf_gather() { return g_opts[17].value.load(std::memory_order_relaxed); }
+int opt_fwd_split_pack() { return g_opts[18].value.load(std::memory_order_relaxed); }
 
 // A library-owned second stream for work that depends only on a call's INPUTS (the counting sorts of the segment reductions)
 // while the caller's stream runs the kernel that produces the data: fork_side makes it wait for everything enqueued on `st` so far,

@@ -39,6 +39,13 @@
 //   * d = 100: the last 4 coordinates are a seventh (mostly zero) tile instead of the fp32 kernel's 4x4x1 blocks + reduce-scatter.
 // Used where it is fewer matrix clocks (NP >= 4) and the planes (3 x 64 B per coordinate and table) leave the workgroup as many waves
 // as the fp32 tables: d = 64 (8 < P <= 32), d = 100 (8 < P <= 20), d = 128 (16 < P <= 20).  fwd_split = 0 runs the fp32 stage 2 everywhere.
+//
+// Packed split stage 2 (McGeom<.., SPLIT_PACK>, option fwd_split_pack, wherever the six-product form applies with P <= 20): a lane holds
+// NS <= 5 logits, so slots 5-7 of every k-quarter multiply zeros in all six MFMAs above.  The 6 NS slot-products of a k-quarter are packed
+// into four MFMAs (NS = 5) or three (NS <= 4) instead: ktup_split_plan.h says which piece of which logit group sits in which slot on both
+// sides and proves, in static_asserts, that every product occurs exactly once.  The A planes are staged from that table (three per table
+// at NS = 5, as before; two at NS <= 4), the B operands are conversions of fp32 vectors arranged by it from the lane's own logits and
+// their residues -- nothing crosses lanes, and a pair stays one MFMA column.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -48,6 +55,7 @@
 #include "ktup_common.h"
 #include "ktup_pref_geom.h"
 #include "ktup_lane_swap.h"
+#include "ktup_split_plan.h"
 
 namespace ktup {
 namespace {
@@ -77,12 +85,62 @@ KTUP_DEV v4 mfma_split(const bf8 ah, const bf8 am, const bf8 al, const Split3& b
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b.hi, acc, 0, 0, 0);
 }
 
-template <int NCH_, int NP_, bool HASE_, bool HARD_, bool SPLIT_ = false>
+// compile-time loop: f(std::integral_constant<int, 0>) .. f(std::integral_constant<int, N - 1>), so that a body can index the constexpr plan
+template <int N, typename F>
+KTUP_DEV void static_for(F&& f) {
+  if constexpr (N > 0) {
+    static_for<N - 1>(f);
+    f(std::integral_constant<int, N - 1>{});
+  }
+}
+// one piece of group `group` of a split vector, or zero, as the plan's term says
+template <int PIECE, int GROUP>
+KTUP_DEV __bf16 plan_piece(const Split3& v) {
+  if constexpr (PIECE == split_plan::HI) return v.hi[GROUP];
+  else if constexpr (PIECE == split_plan::MID) return v.mid[GROUP];
+  else if constexpr (PIECE == split_plan::LO) return v.lo[GROUP];
+  else return (__bf16)0.f;
+}
+// the B operand of MFMA M of the plan as an fp32 vector to convert: the hi piece of group s is bf16(x[s]), the mid piece bf16(r1[s]) with
+// r1 = x - hi, the lo piece bf16(r2[s]) with r2 = r1 - mid
+template <int NS, int M>
+KTUP_DEV f8 plan_b_arranged(const float* x, const float* r1, const float* r2) {
+  f8 v;
+  static_for<8>([&](auto sl) {
+    constexpr split_plan::Term t = split_plan::plan_for(NS).mfma[M].b[decltype(sl)::value];
+    if constexpr (t.piece == split_plan::HI) v[decltype(sl)::value] = x[t.group];
+    else if constexpr (t.piece == split_plan::MID) v[decltype(sl)::value] = r1[t.group];
+    else if constexpr (t.piece == split_plan::LO) v[decltype(sl)::value] = r2[t.group];
+    else v[decltype(sl)::value] = 0.f;
+  });
+  return v;
+}
+// table . logits by the plan: p0 = this lane's chunk of the tile's coordinate in plane 0 (planes PLQ chunks apart), pb = the B operands in
+// issue order (smallest terms first)
+template <int NS, int PLQ>
+KTUP_DEV v4 mfma_packed(const bf8* p0, const bf8 (&pb)[4], v4 acc) {
+  constexpr int NPL = split_plan::plan_for(NS).nplanes, NM = split_plan::plan_for(NS).nmfma;
+  bf8 ap[NPL];
+#pragma unroll
+  for (int pl = 0; pl < NPL; ++pl) ap[pl] = p0[pl * PLQ];
+  static_for<NM>([&](auto m) {
+    constexpr int M = decltype(m)::value;
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[split_plan::plan_for(NS).mfma[M].plane], pb[M], acc, 0, 0, 0);
+  });
+  return acc;
+}
+
+enum { SPLIT_FP32 = 0, SPLIT_SIX = 1, SPLIT_PACK = 2 };   // stage 2 of the soft gate: fp32 MFMAs, six bf16 products, the packed plan
+
+template <int NCH_, int NP_, bool HASE_, bool HARD_, int SPLIT_ = SPLIT_FP32>
 struct McGeom {
   static constexpr int NCH = NCH_, NP = NP_;
   static constexpr bool HASE = HASE_, HARD = HARD_;   // HARD: straight-through Gumbel gate (forward value = one-hot)
-  static constexpr bool SPLIT = SPLIT_;               // soft gate: stage 2 on v_mfma_f32_16x16x32_bf16, operands as three bf16 pieces
+  static constexpr bool SPLIT = SPLIT_ != SPLIT_FP32; // soft gate: stage 2 on v_mfma_f32_16x16x32_bf16, operands as three bf16 pieces
+  static constexpr bool PACK = SPLIT_ == SPLIT_PACK;  //   ... with the products packed by ktup_split_plan.h (NS = NP logits per lane)
+  static constexpr int NPL = PACK ? split_plan::plan_for(NP_).nplanes : 3;   // SPLIT: bf16 planes per table
   static_assert(!(SPLIT && HARD) && !(SPLIT && NP > 8), "the split stage 2 is the soft gate's, K = 32 preference slots");
+  static_assert(!PACK || (NP >= 3 && NP <= 5 && split_plan::plan_for(NP_).ns == NP_), "the packed plans are for three to five logits per lane");
   static constexpr int D = 4 * NCH;
   static constexpr int KG = (D + 15) / 16;               // stage-1 k groups of 16 coordinates
   static constexpr int CT = KG;                          // stage-2 coordinate tiles of 16
@@ -104,7 +162,7 @@ struct McGeom {
   static constexpr int A4_F4 = REM4 ? 4 * 4 * KQ : 0;    // REM4 table: [4 prefs][4 quarters][KQ] float4
   static constexpr int HP = NCH | 1;                     // HARD: odd float4 pitch of the row-major tables (one row is looked up per pair)
   static constexpr int PLANE_Q = 16 * CT * 4;            // SPLIT: 16-byte chunks of one bf16 plane, [16 CT coordinates][4 k-quarters] x 8 slots
-  static constexpr int T_F = SPLIT ? 3 * PLANE_Q * 4 : HARD ? TROW * HP * 4 : TROW * TPITCH;   // floats per stage-2 table (SPLIT: three planes)
+  static constexpr int T_F = SPLIT ? NPL * PLANE_Q * 4 : HARD ? TROW * HP * 4 : TROW * TPITCH;   // floats per stage-2 table (SPLIT: NPL planes)
   static constexpr size_t TABLE_BYTES = (size_t)(A_F4 + A4_F4) * 16 + (size_t)2 * T_F * 4;
   static constexpr int XT_F4 = 16 * NCH + 3;             // x / q tile + 3 zero chunks (stage-1 reads run past the last row)
   static constexpr int NOISE_F = HARD ? 16 * TROW : 0;   // HARD: Gumbel noise of the tile, [pair][preference]
@@ -201,8 +259,22 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
         }
         const Split3 sn = split3(vn), sr = split3(vr);
         const int o = 4 * c + (kqs ^ ((c >> 2) & 2));
-        CnP[o] = sn.hi; CnP[PLQ + o] = sn.mid; CnP[2 * PLQ + o] = sn.lo;
-        ArP[o] = sr.hi; ArP[PLQ + o] = sr.mid; ArP[2 * PLQ + o] = sr.lo;
+        if constexpr (G::PACK) {
+          // the plan's planes: slot sl of plane pl holds the piece the table names, of the group it names (groups >= NP are zero: P <= 4 NP)
+          static_for<G::NPL>([&](auto pl) {
+            bf8 cn, cr;
+            static_for<8>([&](auto sl) {
+              constexpr split_plan::Term tm = split_plan::plan_for(NP).plane[decltype(pl)::value][decltype(sl)::value];
+              cn[decltype(sl)::value] = plan_piece<tm.piece, tm.group>(sn);
+              cr[decltype(sl)::value] = plan_piece<tm.piece, tm.group>(sr);
+            });
+            CnP[decltype(pl)::value * PLQ + o] = cn;
+            ArP[decltype(pl)::value * PLQ + o] = cr;
+          });
+        } else {
+          CnP[o] = sn.hi; CnP[PLQ + o] = sn.mid; CnP[2 * PLQ + o] = sn.lo;
+          ArP[o] = sr.hi; ArP[PLQ + o] = sr.mid; ArP[2 * PLQ + o] = sr.lo;
+        }
       }
     } else {
       constexpr int pitch4 = HARD ? HP : TPITCH / 4;
@@ -533,7 +605,26 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
     // ---- stage 2a: n^T coordinate tiles
     v4 accN[CTF];
     Split3 lgs;                                                  // SPLIT: B[k = 8 kq + s][pair j] = the logit registers in hand, in pieces
-    if constexpr (SPLIT) {
+    bf8 pb[4];                                                   // PACK: the plan's B operands, in issue order
+    if constexpr (G::PACK) {
+      // the last MFMA's operand holds the hi pieces and the one before it the mid pieces, group s in slot s (ktup_split_plan.h,
+      // levels_in_place): the residues come from them, and every operand is ONE conversion of an fp32 vector arranged by the plan
+      constexpr int NM = split_plan::plan_for(NP).nmfma;
+      float x[NP], r1[NP], r2[NP];
+#pragma unroll
+      for (int s = 0; s < NP; ++s) x[s] = lg[s >> 2][s & 3];
+      pb[NM - 1] = __builtin_convertvector(plan_b_arranged<NP, NM - 1>(x, r1, r2), bf8);
+      const f8 hf = __builtin_convertvector(pb[NM - 1], f8);
+#pragma unroll
+      for (int s = 0; s < NP; ++s) r1[s] = x[s] - hf[s];
+      pb[NM - 2] = __builtin_convertvector(plan_b_arranged<NP, NM - 2>(x, r1, r2), bf8);
+      const f8 mf = __builtin_convertvector(pb[NM - 2], f8);
+#pragma unroll
+      for (int s = 0; s < NP; ++s) r2[s] = r1[s] - mf[s];
+      static_for<NM - 2>([&](auto m) { pb[decltype(m)::value] = __builtin_convertvector(plan_b_arranged<NP, decltype(m)::value>(x, r1, r2), bf8); });
+#pragma unroll
+      for (int ct = 0; ct < CTF; ++ct) accN[ct] = mfma_packed<NP, PLQ>(pn0 + 64 * ct, pb, (v4){0.f, 0.f, 0.f, 0.f});
+    } else if constexpr (SPLIT) {
       f8 g;
 #pragma unroll
       for (int sl = 0; sl < 8; ++sl) g[sl] = (sl >> 2) < G::PT ? lg[(sl >> 2) < G::PT ? sl >> 2 : 0][sl & 3] : 0.f;
@@ -596,7 +687,9 @@ __global__ __launch_bounds__(G::NW * 64) void pref_fwd_mc_kernel(McArgs a) {
         if (4 * ct + kq < NCH) qv = xb[4 * ct];
       }
       v4 accR = qv;                                              // q + r: start the accumulator at q
-      if constexpr (SPLIT) {
+      if constexpr (G::PACK) {
+        accR = mfma_packed<NP, PLQ>(pr0 + 64 * ct, pb, accR);
+      } else if constexpr (SPLIT) {
         accR = mfma_split(pr0[64 * ct], pr0[PLQ + 64 * ct], pr0[2 * PLQ + 64 * ct], lgs, accR);
       } else {
 #pragma unroll
@@ -908,11 +1001,21 @@ int launch_mc_e(const McArgs& a, hipStream_t st, const char* name) {
   }
   // option fwd_split: stage 2 on the bf16 matrix pipe, where that is fewer clocks (NP >= 4: six 16-clock MFMAs per tile and table
   // against NP 32-clock ones) and the three bf16 planes leave the workgroup as many waves as the fp32 tables do
-  if constexpr (NCH <= 32 && NP >= 4 && McGeom<NCH, NP, true, false, true>::NW == McGeom<NCH, NP, true, false>::NW &&
-                McGeom<NCH, NP, false, false, true>::NW == McGeom<NCH, NP, false, false>::NW) {
+  if constexpr (NCH <= 32 && NP >= 4 && McGeom<NCH, NP, true, false, SPLIT_SIX>::NW == McGeom<NCH, NP, true, false>::NW &&
+                McGeom<NCH, NP, false, false, SPLIT_SIX>::NW == McGeom<NCH, NP, false, false>::NW) {
     if (opt_fwd_split()) {
-      if (a.E) return launch_mc<McGeom<NCH, NP, true, false, true>>(a, st, name);
-      return launch_mc<McGeom<NCH, NP, false, false, true>>(a, st, name);
+      // option fwd_split_pack: at most five logits per lane (P <= 20) leave slots 5-7 of every k-quarter empty -- the six products packed
+      // into four MFMAs (three at P <= 16) by ktup_split_plan.h; never more LDS than the six-product planes
+      if constexpr (NP <= 5) {
+        static_assert(McGeom<NCH, NP, true, false, SPLIT_PACK>::NW >= McGeom<NCH, NP, true, false, SPLIT_SIX>::NW &&
+                      McGeom<NCH, NP, false, false, SPLIT_PACK>::NW >= McGeom<NCH, NP, false, false, SPLIT_SIX>::NW, "the packed planes fit where the six-product planes do");
+        if (opt_fwd_split_pack()) {
+          if (a.E) return launch_mc<McGeom<NCH, NP, true, false, SPLIT_PACK>>(a, st, name);
+          return launch_mc<McGeom<NCH, NP, false, false, SPLIT_PACK>>(a, st, name);
+        }
+      }
+      if (a.E) return launch_mc<McGeom<NCH, NP, true, false, SPLIT_SIX>>(a, st, name);
+      return launch_mc<McGeom<NCH, NP, false, false, SPLIT_SIX>>(a, st, name);
     }
   }
   if (a.E) return launch_mc<McGeom<NCH, NP, true, false>>(a, st, name);
