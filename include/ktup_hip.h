@@ -869,6 +869,57 @@ int ktup_reg_align_pairs(const float* A, int64_t lda, const float* B, int64_t ld
                          const int64_t* b_ids, const int64_t* n_dev, int64_t n_host, int64_t cap, int l1, float scale, float* loss,
                          float* gA, float* gB, void* stream);
 
+/* =================================================================== CFKG (csrc/ktup_cfkg.hip)
+ * CFKG scores a rating as the TransE triple (user, buy, item-entity): head in the user table, tail in the entity table, relation
+ * the last row of the relation table (CFKG.py:66-80; all-item evaluation CFKG.py:100-118), under the BPR loss of the joint driver
+ * (knowledgable_recommendation.py:335-344).                                                                                     */
+/* ------------------------------------------------------------------ the rec step of CFKG in one launch
+ * u_ids = [u ; u] and i_ids = [pos ; neg], 2B entries each (the layout ktup_feed_rec fills): rows k and k + B are the positive
+ * and the negative pair of example k; only the first B entries of u_ids are read.  With
+ *     z+- = U[u] + R[rel] - E[i+-],     s+- = sum_j |z+-[j]|  (l1 != 0)   or   sum_j z+-[j]^2
+ *     loss[0] += up * mean_k( -logsigmoid(target * (s+[k] - s-[k])) )              (evaluated as max(-x, 0) + log1p(exp(-|x|)))
+ * and with g_k the derivative of that term with respect to s+[k] (-g_k is the one with respect to s-[k]) and v+- = sign(z+-)
+ * (sign(0) = 0, as torch.abs differentiates) or 2 z+-, the gradients are ADDED (float atomics; duplicate users and items in a
+ * batch and pos == neg are fine) to buffers with the pitches of their tables:
+ *     gU[u]   += g (v+ - v-)                       one row add per example: a user is shared by its positive and its negative
+ *     gR[rel] += g (v+ - v-)                       summed over a workgroup's examples on chip: one row add per workgroup
+ *     gE[pos] -= g v+,   gE[neg] += g v-
+ * No other row of gR is touched.  `up`: upstream scalar of the loss (1 / world for data-parallel replicas).  No memset and no
+ * scratch memory: the launch can be captured into a graph.
+ *
+ * Any B >= 1 and 1 <= d <= 256; rows that are 16-byte aligned with d % 4 == 0 (pointers and pitches of every table and gradient)
+ * are loaded as float4, others element by element.  Larger d, or the library option "deterministic" being set (the row adds are
+ * float atomics issued by many workgroups), is KTUP_ERR_UNSUPPORTED: the caller keeps its multi-launch route.
+ * ktup_train_cfkg_rec_step_supported(d): 1 if a launch with this width would be taken (no launch is made), else 0.             */
+int ktup_train_cfkg_rec_step_supported(int d);
+int ktup_train_cfkg_rec_step(const float* U, int64_t ldu, const float* E, int64_t lde, const float* R, int64_t ldr, int64_t rel,
+                             int d, const int64_t* u_ids, const int64_t* i_ids, int64_t B, int l1, float target, float up,
+                             float* loss, float* gU, float* gE, float* gR, void* stream);
+
+/* ------------------------------------------------------------------ scores + filtered top-n of a whole rec evaluation pass
+ * Candidate j (0 <= j < n_cand) is row cand_ids[j] of E; cand_ids == NULL: candidate j is row j, and n_cand must equal n_ent.
+ *     score(b, j) = sum_k |c[k] - e[k]|  (l1 != 0)   or   sum_k (c[k] - e[k])^2,      c = U[u_ids[b]] + R[rel],  e = candidate j
+ * -- what ktup_eval_transe_scores on gathered candidate rows + ktup_eval_topk_filtered(descending = 0) compute batch by batch, in
+ * one sweep that never writes the (users x candidates) matrix.  The ranked list is that of ktup_eval_topk_filtered(descending = 0):
+ * ascending score, ties -> lower j, the j of the user's filter list skipped, -1 padding; top_scores (may be NULL) holds the scores
+ * themselves, 0 in padded slots.  A cand_ids[j] outside [0, n_ent) is never ranked and its row is never read.
+ * The scores are the per-batch route's up to fp32 rounding, NOT bit for bit: the squared L2 distance is evaluated as
+ * (|c|^2 - 2 c.e) + |e|^2 with c.e on the fp32 matrix cores, the L1 distance is summed four columns at a time -- sums associated
+ * differently from the column-by-column chain of ktup_eval_transe_scores.  Two candidates whose distances differ by less than that
+ * rounding may swap places against the per-batch route.
+ *
+ * Any 1 <= d <= 256 (rows that are not 16-byte aligned or d % 4 != 0 are loaded element by element), any pitches, topn <= 16,
+ * n_cand < 2^31, duplicates in u_ids allowed; otherwise KTUP_ERR_UNSUPPORTED and the caller keeps the per-batch calls.  nq == 0
+ * is KTUP_OK and launches nothing.  filt_off / filt_ids: CSR filter sets per user of u_ids, in j space (filt_off[nq + 1]; NULL =
+ * none).  nsplit: into how many contiguous parts the candidates are cut (each part of a block of 64 users is one workgroup); 0 =
+ * chosen by the library, a larger request than the merge takes (512 / topn, at most 32) or the candidates yield is reduced.
+ * `ws`: ktup_eval_cfkg_topk_workspace_bytes bytes for the same arguments, 16-byte aligned.                                     */
+size_t ktup_eval_cfkg_topk_workspace_bytes(int d, int64_t nq, int64_t n_cand, int topn, int nsplit);
+int ktup_eval_cfkg_topk(const float* U, int64_t ldu, const float* R, int64_t ldr, int64_t rel, const float* E, int64_t lde,
+                        int64_t n_ent, const int64_t* cand_ids, int64_t n_cand, int d, const int64_t* u_ids, int64_t nq, int l1,
+                        const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids,
+                        float* top_scores, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -866,6 +866,40 @@ def eval_dot_topk(U, I, u, topn, filt_off=None, filt_ids=None, user_add=None, it
     return (top, ts) if with_scores else top
 
 
+@torch.no_grad()
+def eval_cfkg_topk(U, R, rel, E, u, topn, l1, cand_ids=None, filt_off=None, filt_ids=None, with_scores=False, nsplit=0):
+    """Scores + filtered top-n of a whole rec evaluation pass of CFKG in one sweep (ktup_eval_cfkg_topk): score(b, j) = the L1 or
+    squared L2 distance of U[u_b] + R[rel] to candidate j, which is row cand_ids[j] of E (cand_ids None: row j, every entity), no
+    (users x candidates) matrix; the order of eval_transe + topk_filtered(descending=False), the scores up to fp32 rounding.  Filter
+    ids and the returned ids are in j space.  -> int32 (len(u), topn) ids (-1 padded) [, scores], or None where the entry point
+    declines the shape (topn > 16, d > 256): keep the per-batch calls."""
+    dev = _dev(_table('user table', U)); _table('relation table', R); _table('entity table', E)
+    if R.device != dev or E.device != dev or R.shape[1] != U.shape[1] or E.shape[1] != U.shape[1]:
+        raise L.KtupError('user, relation and entity tables must share the device and the embedding size')
+    if not (0 <= int(rel) < R.shape[0]):
+        raise L.KtupError('relation row %d outside the %d rows of the relation table' % (int(rel), R.shape[0]))
+    u = _ids('u_ids', u, dev)
+    if cand_ids is not None:
+        cand_ids = _ids('cand_ids', cand_ids, dev)
+    nq, d, ne = u.numel(), U.shape[1], E.shape[0]
+    nc = ne if cand_ids is None else cand_ids.numel()
+    if not (0 < topn <= 16) or nq == 0 or nc == 0 or not (0 < d <= 256):
+        return None
+    if filt_ids is not None and filt_ids.numel() == 0:       # an empty id list has no storage to point at: same as no filter
+        filt_off = filt_ids = None
+    top = torch.empty(nq, topn, dtype=torch.int32, device=dev)
+    ts = torch.empty(nq, topn, dtype=torch.float32, device=dev) if with_scores else None
+    ws = _scratch(L.load().ktup_eval_cfkg_topk_workspace_bytes(d, nq, nc, int(topn), int(nsplit)), dev)
+    try:
+        L.call('ktup_eval_cfkg_topk', _p(U), U.stride(0), _p(R), R.stride(0), int(rel), _p(E), E.stride(0), ne, _p(cand_ids), nc, d, _p(u), nq,
+               int(bool(l1)), _p(filt_off), _p(filt_ids), int(topn), int(nsplit), _p(top), _p(ts), _p(ws), _stream(dev))
+    except L.KtupError as e:
+        if e.code == L.ERR_UNSUPPORTED:
+            return None
+        raise
+    return (top, ts) if with_scores else top
+
+
 def eval_tup(U, I, pref, pref_norm, u, l1, gumbel_mode=GUMBEL_OFF, uniform=None, seed=0, offset=0, items=None):
     """transUP.py:84-102 -> (len(u), n_items).  `items`: eval_pref_items(...) of the same tables (one per evaluation pass)."""
     return _eval_pref(U, I, None, pref, pref_norm, None, None, None, u, l1, gumbel_mode, uniform, seed, offset, items)

@@ -1,5 +1,6 @@
 """CFKG with the reference's class surface (jTransUP/models/CFKG.py): TransE over users, item-entities and relations, with one
-extra "buy" relation (the last row of the relation table) between a user and an item -- a thin module over the K2 / K12 kernels.
+extra "buy" relation (the last row of the relation table) between a user and an item -- a thin module over the K2 / K12 kernels,
+with the whole rec evaluation pass behind one call (evaluate_topk; the training step: utils/fast_train_dot.py).
 
 Ratings are triples (user, buy, item) whose head lives in the USER table and whose tail in the shared item / entity table
 (CFKG.py:62, 66-80).  K2 gathers heads and tails from one table, so the rec branch scores on the row-stack [users ; entities]
@@ -57,6 +58,17 @@ class CFKG(nn.Module, GradToggle):
         buy = torch.full_like(u_ids, self.rel_total - 1)
         return ops.eval_transe(self.user_embeddings.weight, self.rel_embeddings.weight, u_ids, buy, self.L1_flag, head=False,
                                candidates=cand.detach().contiguous())
+
+    topk_descending = False          # evaluate_topk ranks ascending distance (the inner-product models: True)
+    topk_takes_candidates = True     # ... and takes the candidates as entity-row ids: the route that serves -share_embeddings
+
+    def evaluate_topk(self, u_ids, items, topn, filt_off=None, filt_ids=None):
+        """The whole rec evaluation pass in one sweep (ktup_eval_cfkg_topk): evaluateRec's scores of every user of `u_ids` against
+        the entity rows `items` (int64 ids; None = every row) AND their filtered top-n, without the (users x candidates) matrix.
+        Ids in the filter lists and in the result are positions in `items`.  -> int32 (len(u_ids), topn), -1 padded, or None where
+        the kernel declines the shape (the caller keeps the batch walk)."""
+        return ops.eval_cfkg_topk(self.user_embeddings.weight, self.rel_embeddings.weight, self.rel_total - 1, self.item_embeddings.weight,
+                                  u_ids, topn, self.L1_flag, cand_ids=items, filt_off=filt_off, filt_ids=filt_ids)
 
     def _cand(self, all_e_ids):
         return self.ent_embeddings(all_e_ids).detach().contiguous() if all_e_ids is not None else None

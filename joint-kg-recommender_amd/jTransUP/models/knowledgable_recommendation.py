@@ -43,6 +43,14 @@ def getMappedItems(e_ids, e_remap, new_map):
     return new_e_ids, i_ids
 
 
+def _pass_candidates(model, i_map):
+    """The item -> entity-row ids of the whole-pass route as ONE device tensor per run, cached on the model per `i_map` identity."""
+    hit = getattr(model, '_pass_cand', None)
+    if hit is None or hit[0] is not i_map:
+        hit = model._pass_cand = (i_map, D.ids([i_map[i] for i in range(len(i_map))]))
+    return hit[1]
+
+
 def evaluateRec(FLAGS, model, eval_iter, eval_dict, all_dicts, i_map, logger, eval_descending=True, is_report=False):
     all_i_var = D.ids([i_map[i] for i in range(len(i_map))]) if FLAGS.share_embeddings else None
     model.eval(); model.disable_grad()
@@ -60,12 +68,21 @@ def evaluateRec(FLAGS, model, eval_iter, eval_dict, all_dicts, i_map, logger, ev
     # (KTUP prepares an item side; the inner-product models -- CKE, coFM -- have none and sweep their tables as they are)
     pass_fn = (lambda u, fo, fi, n: model.evaluate_topk(u, model.prepare_items() if has_items else None, n, fo, fi)) \
         if hasattr(model, 'evaluate_topk') and not FLAGS.share_embeddings else None
+    graph_key = D.model_graph_key(model) if pass_fn else None
+    if pass_fn is None and FLAGS.share_embeddings and getattr(model, 'topk_takes_candidates', False):
+        # CFKG: the candidates are entity rows, given as ids.  A captured pass (D._rec_eval_fused) reads them on every replay, so the id
+        # tensor is built once per run and kept alive on the model -- `all_i_var` above is a new tensor on every call -- and its address
+        # is part of what the capture depends on
+        cand = _pass_candidates(model, i_map)
+        pass_fn = lambda u, fo, fi, n: model.evaluate_topk(u, cand, n, fo, fi)
+        graph_key = D.model_graph_key(model)
+        graph_key = None if graph_key is None else graph_key + (cand.data_ptr(),)
     native = getattr(model, '_shard_native', None)             # -shard_tables: the candidates are the rows this rank owns
     if native is not None and not is_report:
         results = D.rec_eval_pass(FLAGS, None, eval_iter, eval_dict, all_dicts, eval_descending, want_rows=False, shard=native.rec_shard())
     else:
         results = D.rec_eval_pass(FLAGS, score_fn, eval_iter, eval_dict, all_dicts, eval_descending, want_rows=is_report,
-                                  shard=rec_shard_fn(model), pass_fn=pass_fn, graph_key=D.model_graph_key(model) if pass_fn else None,
+                                  shard=rec_shard_fn(model), pass_fn=pass_fn, graph_key=graph_key,
                                   pass_descending=getattr(model, 'topk_descending', False))
     perf = D.summarize_rec(FLAGS, results, logger)
     if is_report:
@@ -107,6 +124,11 @@ def evaluateKG(FLAGS, model, eval_head_iter, eval_tail_iter, eval_head_dict, eva
 def _dot_step_supported(d):
     from jTransUP.utils.fast_train_dot import dot_step_supported
     return dot_step_supported(d)
+
+
+def _cfkg_step_supported(d):
+    from jTransUP.utils.fast_train_dot import cfkg_step_supported
+    return cfkg_step_supported(d)
 
 
 def train_loop(FLAGS, model, trainer, rating_train_dataset, triple_train_dataset, rating_eval_datasets, triple_eval_datasets, e_map,
@@ -160,16 +182,17 @@ def train_loop(FLAGS, model, trainer, rating_train_dataset, triple_train_dataset
             kg_feed = DeviceFeeder(triple_train_list, FLAGS.batch_size, D.DEV, FLAGS.negtive_samples, seed=FLAGS.seed + 1)
             stepper.attach_feeds(sampler, rec=rec_feed, kg=kg_feed)
             logger.info('Training data and negative sampling are device-resident (-device_sampling).')
-    elif D.USE_CUDA and FLAGS.model_type in ('cofm', 'cke') and trainer.fused is not None \
-            and os.environ.get('KTUP_FAST_TRAIN', '1') != '0' and _dot_step_supported(FLAGS.embedding_size):
+    elif D.USE_CUDA and FLAGS.model_type in ('cofm', 'cke', 'cfkg') and trainer.fused is not None \
+            and os.environ.get('KTUP_FAST_TRAIN', '1') != '0' \
+            and (_cfkg_step_supported if FLAGS.model_type == 'cfkg' else _dot_step_supported)(FLAGS.embedding_size):
         # coFM / CKE: ktup_train_dot_step for the rec step, the existing TransE / TransR launches for the kg step, the alignment
-        # term (coFM with its own item table) on the device (utils/fast_train_dot.py)
+        # term (coFM with its own item table) on the device; CFKG: ktup_train_cfkg_rec_step and coFM's kg step (utils/fast_train_dot.py)
         from jTransUP.utils.fast_train_dot import BaselineJointStepper
         stepper = baseline = BaselineJointStepper(model, trainer, FLAGS, FLAGS.batch_size)
         logger.info('GPU-resident training step enabled (KTUP_FAST_TRAIN=0 selects the autograd route).')
         if FLAGS.device_sampling:
             logger.info('-device_sampling: the joint baselines take host-fed batches only; running as under -nodevice_sampling.')
-    D.require_stepper_for_replicas(stepper, 'jtransup -noshare_embeddings, cofm, cke')
+    D.require_stepper_for_replicas(stepper, 'jtransup -noshare_embeddings, cofm, cke, cfkg')
     logger.info('Training.')
 
     def do_eval(totals):
@@ -229,7 +252,7 @@ def train_loop(FLAGS, model, trainer, rating_train_dataset, triple_train_dataset
             ph, pt, pr = kg_feed.next_cols()               # (h, t, r): tail before relation, like the files
             nh, nt = sampler.sample_kg(ph, pt, pr)
             return 'kg', stepper.kg_step(ph, pt, pr, nh, nt, pr)
-        if baseline is not None:                           # coFM / CKE: the id handling of the autograd route below, then the stepper
+        if baseline is not None:                           # coFM / CKE / CFKG: the id handling of the autograd route below, then the stepper
             if is_rec:
                 u, pi, ni = getNegRatings(next(rating_train_iter), item_total, all_dicts=all_rating_dicts)
                 align = getMappedEntities(pi + ni, i_map, ikg_map) if baseline.align else None

@@ -1,5 +1,5 @@
 """GPU-resident training steps of the inner-product recommenders: FM (item_recommendation.py:160-195 -> DotRecStepper) and the joint
-baselines coFM and CKE (knowledgable_recommendation.py:330-401 -> BaselineJointStepper), on the machinery of utils/fast_train.py
+baselines coFM, CKE and CFKG (knowledgable_recommendation.py:330-401 -> BaselineJointStepper), on the machinery of utils/fast_train.py
 (flat gradient bucket, data-parallel slice + all-reduce, pre-bound launches, HIP-graph replay, the K20 clip + step).
 
 Their rec step is one computation -- the inner product of a user row with an item-side row, optional bias terms, the BPR loss, the
@@ -7,7 +7,8 @@ gradients back into the gathered rows -- and ONE launch: ktup_train_dot_step (in
 ktup_optim_clip_step.  The kg side takes what exists: ktup_train_kg_step (TransE) for coFM, the TransR launches of KGStepper for
 CKE.  coFM with its own item table adds the alignment term of knowledgable_recommendation.py:385-390 to EVERY step:
 ktup_reg_align_pairs, whose id lists the host builds exactly as the autograd route does (getMappedEntities / getMappedItems on the
-global batch) and copies, with their length, into fixed buffers outside the graph.
+global batch) and copies, with their length, into fixed buffers outside the graph.  CFKG's rec step is a translation, not an
+inner product (user + buy - item-entity, CFKG.py:66-80): ONE launch of its own, ktup_train_cfkg_rec_step; its kg step is coFM's.
 
 rec step:  bprLoss(pos, neg, target)                                                   [+ norm_lambda * pNormLoss(ent rows, item rows)]
 kg step:   kg_lambda * (marginLoss(pos, neg, margin) + normLoss(ent rows) + normLoss(rel rows))     [+ the same alignment term]
@@ -16,6 +17,11 @@ import torch
 
 from jTransUP.hip import lib as L
 from jTransUP.utils.fast_train import _StepperBase, _p
+
+
+def cfkg_step_supported(d):
+    """Whether ktup_train_cfkg_rec_step takes this width (and the library option `deterministic` is off): the driver's condition."""
+    return bool(L.load().ktup_train_cfkg_rec_step_supported(int(d)))
 
 
 def dot_step_supported(d):
@@ -64,7 +70,7 @@ class DotRecStepper(_StepperBase):
 
 
 class BaselineJointStepper(_StepperBase):
-    """coFM (either setting of -share_embeddings) and CKE.
+    """coFM (either setting of -share_embeddings), CKE and CFKG (whose item table IS the entity table: no alignment term).
 
     A table joins the optimizer step with the first step that can give it a gradient, as on the autograd route, where a
     parameter's `.grad` is None until its first backward and the optimizer skips it until then (no weight decay, no moment decay,
@@ -81,11 +87,13 @@ class BaselineJointStepper(_StepperBase):
         m, B = self.m, self.B
         self.kg_lambda, self.norm_lambda = float(FLAGS.kg_lambda), float(FLAGS.norm_lambda)
         self.cke = hasattr(m, 'proj_embeddings')
+        self.cfkg = not self.cke and not hasattr(m, 'user_bias')       # tables (U, E, R): the rec score is a translation
         U, E, R = m.user_embeddings.weight, m.ent_embeddings.weight, m.rel_embeddings.weight
         I = m.item_embeddings.weight                                    # coFM -share_embeddings: the entity table itself
         d = U.shape[1]
-        if not dot_step_supported(d):
-            raise L.KtupError('ktup_train_dot_step does not take embedding_size %d (or KTUP_DETERMINISTIC=1 is set)' % d)
+        if not (cfkg_step_supported(d) if self.cfkg else dot_step_supported(d)):
+            raise L.KtupError('%s does not take embedding_size %d (or KTUP_DETERMINISTIC=1 is set)'
+                              % ('ktup_train_cfkg_rec_step' if self.cfkg else 'ktup_train_dot_step', d))
         self.gstate = None
         self.lam = torch.full((), self.kg_lambda, **f32)               # upstream gradient of the multi-launch kg terms
         self._id_buffers('rec', i64); self._id_buffers('kg', i64)
@@ -97,6 +105,14 @@ class BaselineJointStepper(_StepperBase):
             self.rws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=self.dev)
             self.align = False
             self.fused_step = False                                     # the TransR kg step is several launches: not device-fed
+        elif self.cfkg:
+            if I is not E:
+                raise L.KtupError('CFKG scores items on the entity table (-share_embeddings is forced)')
+            self.tabs = (U, E, R)
+            touch = {'rec': (U, E, R), 'kg': (E, R)}                    # the buy relation is a row of R: R wakes with either kind
+            self.align = False
+            self.kg_fused = bool(self.want_fused and L.load().ktup_train_step_supported(2, d, 0))
+            self.fused_step = False                                     # host-fed only
         else:
             bu, bi, gb = m.user_bias.weight, m.item_bias.weight, m.bias
             shared = I is E
@@ -170,11 +186,17 @@ class BaselineJointStepper(_StepperBase):
                 b('ktup_reg_norm_fused', _p(E), E.stride(0), d, _p(self.ht4), 4 * B, _p(self.lam), _p(self.loss[2:]), g(E), st),
                 b('ktup_reg_norm_fused', _p(R), R.stride(0), d, _p(self.r2), 2 * B, _p(self.lam), _p(self.loss[3:]), g(R), st)]
             return
-        U, bu, bi, gb, R, E = self.tabs[:6]
-        I = self.tabs[6] if self.align else E
-        d = U.shape[1]
-        self._rec_fused = b('ktup_train_dot_step', _p(U), U.stride(0), _p(I), I.stride(0), None, 0, None, -1, _p(gb), _p(bu), _p(bi), d,
-                            _p(self.u2), _p(self.i2), B, self.target, inv, _p(self.loss), g(U), g(I), None, g(bi), st)
+        if self.cfkg:
+            U, E, R = self.tabs
+            d = U.shape[1]
+            self._rec_fused = b('ktup_train_cfkg_rec_step', _p(U), U.stride(0), _p(E), E.stride(0), _p(R), R.stride(0), m.rel_total - 1, d,
+                                _p(self.u2), _p(self.i2), B, self.l1, self.target, inv, _p(self.loss), g(U), g(E), g(R), st)
+        else:
+            U, bu, bi, gb, R, E = self.tabs[:6]
+            I = self.tabs[6] if self.align else E
+            d = U.shape[1]
+            self._rec_fused = b('ktup_train_dot_step', _p(U), U.stride(0), _p(I), I.stride(0), None, 0, None, -1, _p(gb), _p(bu), _p(bi), d,
+                                _p(self.u2), _p(self.i2), B, self.target, inv, _p(self.loss), g(U), g(I), None, g(bi), st)
         if self.kg_fused:
             self._kg_fused = b('ktup_train_kg_step', 0, _p(E), E.stride(0), _p(R), R.stride(0), None, 0, d, _p(self.h2), _p(self.t2),
                                _p(self.r2), B, self.l1, self.margin, self.kg_lambda, 6, _p(self.loss), g(E), g(R), None, None, st)
@@ -240,7 +262,7 @@ class BaselineJointStepper(_StepperBase):
         return self._finish('kg', 4, self.kg_lambda)
 
     def rec_step(self, u, pi, ni, align=None):
-        """u, pi, ni: int64 device tensors of the GLOBAL batch (coFM -share_embeddings: pi, ni already mapped to entity rows).
+        """u, pi, ni: int64 device tensors of the GLOBAL batch (coFM -share_embeddings and CFKG: pi, ni already mapped to entity rows).
         align = (entity ids, item ids), coFM with its own item table only.  Returns the step's loss (0-dim device tensor)."""
         self._wake('rec')
         self._take_alignment(align)
