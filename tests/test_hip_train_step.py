@@ -1,0 +1,571 @@
+"""GPU parity of the fused training-step kernels through the C ABI (jTransUP.hip.lib.call) against tests/_train_step_ref.py: fp64
+autograd on the CPU, through the oracle, from the same fp32 inputs.  ktup_train_rec_step (the STEP form of pref_bwd_wide_kernel,
+csrc/ktup_score_pref_bwd_wide.hip), ktup_train_kg_step (kg_step_kernel, csrc/ktup_train_step.hip) and the stored-row forms
+ktup_train_rec_step_rows[_ws], ktup_train_rec_reg_rows and ktup_train_kg_step_rows (csrc/ktup_shard_kg.hip).
+
+The tables are small so that rows collide (7 users, 11 items, 9 entities + the pad row; 9 entities and 4 relations for kg); the
+cases hold no knife edge (see the reference module: asserted on the fp64 reference before anything is launched; the number of
+seeds every family needed is printed by test_redraw_counts_stay_small).
+
+Tolerances are the project's own: loss slots rtol 1e-4; gradients rtol 1e-4, atol max(3e-5, 2e-6 max|want|) (test_hip_dot_step.py,
+test_hip_score.py); tracked norm and sumsq 2e-5 relative (test_fast_train.py, test_numeric_claims.py).  Every case also asserts
+that the columns between d and the pitch, the pad entity row and the rows no id touches stay EXACTLY zero, and prints
+max|got - want| and max|want| per buffer.
+
+Which instantiation family a test launches (rec: d x NP class x {TUP, KTUP} x {soft, hard} x {atomics, rows}; NP class = ceil(P / 4)
+rounded up to 4, 5 or 8: P 1, 16 -> 4; 17, 20 -> 5; 21, 32 -> 8; kg: lane-group width 16 / 32 / 64 x {TransE, TransH}):
+
+  test_rec_step_grid              d 64/100/128 x NP 4/5/8, d 256 x NP 4/5 (8: refused) x TUP/KTUP x soft/hard, atomics, B = 13
+  test_rec_step_batch_sizes       d x NP 5, KTUP soft + TUP hard, atomics, B 1 .. 67 (dead slots, one tile, several workgroups)
+  test_rec_step_options           pitches, target, gscale, accumulate: d 100 / 256, NP 5, KTUP
+  test_rec_step_wide_waves        d 256 four-wave <64,4,NP> and eight-wave <64,2,NP,8> forms, NP 4 / 5
+  test_rec_step_grid_stride       d x NP 5: the tile loop with its double-buffered ids; _deterministic: one workgroup, nine tiles
+  test_rec_step_tracked_norm      d 64/100/128 x NP 5, atomics with returned values (TRK)
+  test_rec_rows                   d x NP 4 (P 4) / 5 (P 20) x TUP/KTUP x soft/hard, rows: plain, replicas, shared gR, id columns
+                                  (the NP 8 rows form, P 21 .. 32 at d <= 128, is NOT launched by any case here)
+  test_rec_reg_rows               reg_rows_kernel at group widths 16 (d 64), 32 (d 100), 64 (d 256)
+  test_kg_step_shapes             d 4 (GL 16), 20 (16), 36 (16), 64 (16), 100 (32), 128 (32), 132 (64), 256 (64) x TransE/TransH
+  test_kg_step_regs_and_margin, _options, _exact_zero, _tracked_norm, _grid_stride, _deterministic     the same kernels
+  test_kg_rows                    kg_step_rows_kernel at GL 16 (d 36), 32 (d 100), 64 (d 256) x TransE/TransH"""
+import pytest
+import torch
+
+from tests import _train_step_ref as R
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+GUMBEL_OFF, GUMBEL_INPUT = 0, 1
+DS = (64, 100, 128, 256)
+PS = (1, 16, 17, 20, 21, 32)
+SENTINEL = 7.0
+
+
+def lib():
+    from jTransUP.hip import lib as L
+    return L
+
+
+def p(t):
+    return None if t is None else t.data_ptr()
+
+
+def close_grad(got, want, what):
+    got = got.detach().cpu()
+    print('%-4s max |got - want| %.3g, max |want| %.3g' % (what, float((got.double() - want).abs().max()), float(want.abs().max())))
+    want = want.to(torch.float32)
+    torch.testing.assert_close(got, want, rtol=1e-4, atol=max(3e-5, 2e-6 * float(want.abs().max())), msg=lambda m: what + ': ' + m)
+
+
+def close_loss(got, want, what='loss'):
+    got = [float(x) for x in got.detach().cpu()]
+    print(what, 'got', ' '.join('%.9g' % x for x in got), 'want', ' '.join('%.9g' % x for x in want))
+    for g, w in zip(got, want):
+        if w == 0.0:
+            assert g == 0.0, what
+        else:
+            assert abs(g - w) <= 1e-4 * abs(w), what
+
+
+def close_sum(got, want, what):
+    print('%s got %.12g want %.12g (relative %.3g)' % (what, got, want, abs(got - want) / want))
+    assert abs(got - want) <= 2e-5 * want, what
+
+
+def untouched_rows_are_zero(buf, n_rows, ids):
+    hit = torch.zeros(n_rows, dtype=torch.bool)
+    hit[ids] = True
+    if bool((~hit).any()):
+        assert float(buf.cpu()[~hit].abs().max()) == 0.0
+
+
+def option(name, value):
+    class _Option:
+        def __enter__(self):
+            self.old = lib().set_option(name, value)
+
+        def __exit__(self, *exc):
+            lib().set_option(name, self.old)
+    return _Option()
+
+
+def seed_of(*parts):
+    s = 17
+    for x in parts:
+        s = (s * 131 + int(x)) % 1000003
+    return s
+
+
+# ==================================================================================================== rec step
+REC_TABLES = ('U', 'I', 'E', 'P', 'Pn', 'R', 'Rn')
+
+
+def rec_device(c):
+    dev = {k: c[k].to(DEV) for k in ('U', 'I', 'P', 'Pn')}
+    for k in ('E', 'R', 'Rn'):
+        dev[k] = c[k].to(DEV) if c['ktup'] else None
+    dev['i2e'] = c['i2e'].to(DEV, torch.int32) if c['ktup'] else None
+    dev['uni'] = c['uni'].to(DEV) if c['hard'] else None
+    dev['u2'] = torch.cat([c['u'], c['u']]).to(DEV)
+    dev['i2'] = torch.cat([c['pi'], c['ni']]).to(DEV)
+    return dev
+
+
+def rec_buffers(c):
+    d, P = c['d'], c['n_pref']
+    b = {'loss': torch.zeros(2, device=DEV), 'U': torch.zeros(c['nu'], c['ldu'], device=DEV), 'I': torch.zeros(c['nitems'], c['ldi'], device=DEV),
+         'P': torch.zeros(P, d, device=DEV), 'Pn': torch.zeros(P, d, device=DEV), 'E': None, 'R': None, 'Rn': None}
+    if c['ktup']:
+        b.update(E=torch.zeros(c['ne'] + 1, c['lde'], device=DEV), R=torch.zeros(P, d, device=DEV), Rn=torch.zeros(P, d, device=DEV))
+    return b
+
+
+def rec_launch(c, dev, b, target, gscale, orth, gnorm=None):
+    kt = c['ktup']
+    lib().call('ktup_train_rec_step', p(dev['U']), c['ldu'], p(dev['I']), c['ldi'], p(dev['E']), c['lde'] if kt else 0, p(dev['i2e']),
+               c['ne'] if kt else -1, p(dev['P']), p(dev['Pn']), p(dev['R']), p(dev['Rn']), c['d'], c['n_pref'], c['d'], p(dev['u2']), p(dev['i2']),
+               c['B'], int(c['l1']), GUMBEL_INPUT if c['hard'] else GUMBEL_OFF, p(dev['uni']), 0, 0, float(target), float(gscale), int(orth),
+               p(b['loss']), p(b['U']), p(b['I']), p(b['E']), p(b['P']), p(b['Pn']), p(b['R']), p(b['Rn']), p(gnorm), None)
+    torch.cuda.synchronize()
+
+
+def rec_compare(c, b, loss, want, times=1):
+    d = c['d']
+    close_loss(b['loss'], [times * x for x in loss])
+    i2 = torch.cat([c['pi'], c['ni']])
+    for k in REC_TABLES:
+        if b[k] is None:
+            assert k not in want
+            continue
+        close_grad(b[k][:, :d], times * want[k], k)
+        if b[k].shape[1] > d:
+            assert float(b[k][:, d:].abs().max()) == 0.0            # nothing lands between the rows
+    untouched_rows_are_zero(b['U'], c['nu'], c['u'])
+    untouched_rows_are_zero(b['I'], c['nitems'], i2)
+    if c['ktup']:
+        assert float(b['E'][c['ne']].abs().max()) == 0.0            # the pad row: exactly, never written
+        untouched_rows_are_zero(b['E'], c['ne'] + 1, c['i2e'][i2])
+
+
+def rec_check(c, target=-1.0, gscale=1.0, orth=1, times=1):
+    loss, want = R.rec_reference(c, target, gscale, orth)
+    dev, b = rec_device(c), rec_buffers(c)
+    for _ in range(times):
+        rec_launch(c, dev, b, target, gscale, orth)
+    rec_compare(c, b, loss, want, times)
+    return b
+
+
+def np_class_member(P):
+    return PS.index(P) % 2          # the two P of an NP class
+
+
+@pytest.mark.parametrize('hard', [False, True])
+@pytest.mark.parametrize('ktup', [False, True])
+@pytest.mark.parametrize('P', PS)
+@pytest.mark.parametrize('d', DS)
+def test_rec_step_grid(d, P, ktup, hard):
+    """B = 13: one full tile and a partial one, on either side of the NP boundaries 16|17 and 20|21, P = 1 and P = 32.  L1 / L2
+    alternate between the two P of an NP class and orth with (model, gate), so each appears with every (d, NP class)."""
+    l1, orth = np_class_member(P) == 0, (int(ktup) + int(hard)) % 2
+    c = R.rec_case(d, P, 13, ktup, hard, l1, seed_of(d, P, ktup, hard), family='rec grid')
+    supported = lib().load().ktup_train_step_supported(0, d, P)
+    if d == 256 and P > 20:
+        assert supported == 0
+        dev, b = rec_device(c), rec_buffers(c)
+        with pytest.raises(lib().KtupError) as err:
+            rec_launch(c, dev, b, -1.0, 1.0, orth)
+        assert err.value.code == lib().ERR_UNSUPPORTED
+        torch.cuda.synchronize()
+        for k, v in b.items():
+            assert v is None or float(v.abs().max()) == 0.0, k      # and nothing was written
+        return
+    assert supported == 1
+    rec_check(c, -1.0, 1.0, orth)
+
+
+@pytest.mark.parametrize('B', [1, 7, 8, 9, 64, 67])
+@pytest.mark.parametrize('d', DS)
+def test_rec_step_batch_sizes(d, B):
+    """P = 20.  B < 8 and B % 8 != 0: the dead slots of a tile gather row 0 -- user 0, item 0 and item 0's entity, all three of norm
+    3 -- and must contribute nothing.  What this can see is a leak on ONE side of a dead slot (by hand: with the positive half of a
+    dead slot keeping its BPR gradient, the cases with B % 8 != 0 fail on the preference-table gradients).  A leak on both sides is
+    invisible to any test of the outputs: both halves gather the same user 0, item 0 and uniform row 0, score alike, and their
+    gradients +g and -g cancel in the table gradients (the row adds are guarded separately)."""
+    rec_check(R.rec_case(d, 20, B, True, False, B % 2 == 0, seed_of(d, B, 1), family='rec batch'), -1.0, 1.0, 1)
+    rec_check(R.rec_case(d, 20, B, False, True, B % 2 == 1, seed_of(d, B, 2), family='rec batch'), -1.0, 1.0, 0)
+
+
+@pytest.mark.parametrize('d', [100, 256])
+def test_rec_step_options(d):
+    """Pitches of d + 4 and d + 12 on U, I and E; target +1 and -1; gscale 0.25 (gradients scale, values do not); two launches
+    into the same buffers give twice the values."""
+    rec_check(R.rec_case(d, 20, 13, True, False, False, seed_of(d, 3), pitch=(4, 12, 4), family='rec options'), -1.0, 1.0, 1)
+    rec_check(R.rec_case(d, 20, 13, True, True, True, seed_of(d, 4), pitch=(12, 4, 12), family='rec options'), 1.0, 1.0, 1)
+    c = R.rec_case(d, 20, 13, True, False, False, seed_of(d, 5), family='rec options')
+    rec_check(c, 1.0, 1.0, 0)
+    rec_check(c, -1.0, 0.25, 1)
+    rec_check(c, -1.0, 1.0, 1, times=2)
+    rec_check(R.rec_case(d, 20, 13, False, False, True, seed_of(d, 6), pitch=(4, 12, 0), family='rec options'), 1.0, 0.25, 1, times=2)
+
+
+@pytest.mark.parametrize('waves', [4, 8])
+@pytest.mark.parametrize('P', [16, 20])
+def test_rec_step_wide_waves(P, waves):
+    """d = 256 with four waves x 64 coordinates and with eight x 32 (option wide_waves)."""
+    with option('wide_waves', waves):
+        rec_check(R.rec_case(256, P, 13, True, True, False, seed_of(P, waves, 7), family='rec waves'), -1.0, 1.0, 1)
+        rec_check(R.rec_case(256, P, 67, False, False, True, seed_of(P, waves, 8), family='rec waves'), -1.0, 1.0, 0)
+
+
+def rec_lds_bytes(d, P, hard, waves=4):
+    """WGeom::LDS of csrc/ktup_score_pref_bwd_wide.hip for the instantiation launch_d picks."""
+    nch, ctw, nwc = {64: (16, 1, 4), 100: (25, 2, 4), 128: (32, 2, 4), 256: (64, 4, 4) if waves == 4 else (64, 2, 8)}[d]
+    np_ = (P + 3) // 4
+    np_ = 4 if np_ <= 4 else 5 if np_ <= 5 else 8
+    ncw = 4 * ctw
+    pt = (np_ + 3) // 4
+    trow = 16 * pt
+    tab_f4 = (4 * np_ + 1) * (nwc * ncw + 1)
+    tile_f4 = 16 * (ncw + 1)
+    red_f = nwc * 64 * pt * 4
+    shared = 3 * tab_f4 * 16 + (2 if nwc <= 4 else 1) * red_f * 4 + 4 * nwc * 16 * 4 + 2 * trow * 17 * 4
+    wave = (3 * tile_f4 * 16 + 2 * 3 * 16 * 4 + (16 * trow if hard else 0) * 4 + 15) & ~15
+    return shared + nwc * wave
+
+
+def rec_grid_stride_batch(d, P, hard):
+    """launch_r starts min(tiles, 256 x per_cu) workgroups, per_cu = floor(160 KB / LDS) of the instantiation (at least 1), and a
+    tile is 8 examples.  256 per_cu + 2 tiles make workgroups 0 and 1 walk two tiles each; five examples in the last one."""
+    per_cu = max(1, (160 * 1024) // rec_lds_bytes(d, P, hard))
+    return 8 * (256 * per_cu + 1) + 5
+
+
+BIG = {'nu': 300, 'nitems': 400, 'ne': 350}
+
+
+@pytest.mark.parametrize('d', DS)
+def test_rec_step_grid_stride(d):
+    """The grid-stride tile loop with its double-buffered id and scratch copies.  P = 20 (NP = 5), four waves, soft gate: LDS is
+    54.5 KB at d = 64 (two workgroups per CU fit 160 KB: 512 workgroups, B = 8 x 513 + 5 = 4109), 82 KB at d = 100 and 128 and 138 KB
+    at d = 256 (one per CU: 256 workgroups, B = 8 x 257 + 5 = 2061).  The hard gate of the d = 100 and 128 cases adds a 2 KB noise
+    tile per wave (90 KB): still one workgroup per CU.  rec_lds_bytes restates WGeom::LDS, so a change of the kernel's geometry
+    that moves these counts fails the assertion on B below.
+    A few hundred table rows keep the row sharing moderate, and the project's tolerances hold."""
+    ktup, hard = d in (64, 128), d in (100, 128)
+    B = rec_grid_stride_batch(d, 20, hard)
+    assert B == (4109 if d == 64 else 2061)
+    rec_check(R.rec_case(d, 20, B, ktup, hard, d == 100, seed_of(d, 9), sizes=BIG, family='rec stride'), -1.0, 1.0, 1)
+
+
+@pytest.mark.parametrize('d', DS)
+def test_rec_step_deterministic(d):
+    """Option deterministic: ONE workgroup walks all nine tiles of B = 67."""
+    with option('deterministic', 1):
+        rec_check(R.rec_case(d, 20, 67, True, d in (64, 256), d == 128, seed_of(d, 10), family='rec stride'), -1.0, 1.0, 1)
+
+
+def tracked_norm(ws):
+    host = ws.cpu()
+    which = int(host.view(torch.int64)[1])
+    assert which in (0, 1)
+    return float(host[8 + 16 * which: 8 + 16 * which + 16].sum())
+
+
+@pytest.mark.parametrize('ktup,hard', [(True, False), (False, True)])
+@pytest.mark.parametrize('d', [64, 100, 128])
+def test_rec_step_tracked_norm(d, ktup, hard):
+    """gnorm: the sum of the 16 slots of the set named by word 1 is the squared norm of the gradients -- here of the REFERENCE's,
+    B = 67 on 7 users and 11 items: every row is shared many times."""
+    c = R.rec_case(d, 20, 67, ktup, hard, False, seed_of(d, ktup, 11), family='rec norm')
+    loss, want = R.rec_reference(c, -1.0, 1.0, 1)
+    dev, b = rec_device(c), rec_buffers(c)
+    ws = torch.zeros(64, dtype=torch.float64, device=DEV)
+    rec_launch(c, dev, b, -1.0, 1.0, 1, gnorm=ws)
+    rec_compare(c, b, loss, want)
+    close_sum(tracked_norm(ws), float(sum((g ** 2).sum() for g in want.values())), 'tracked squared norm')
+
+
+def test_rec_step_tracked_norm_is_refused_at_256():
+    c = R.rec_case(256, 20, 13, True, False, False, seed_of(12), family='rec norm')
+    dev, b = rec_device(c), rec_buffers(c)
+    ws = torch.zeros(64, dtype=torch.float64, device=DEV)
+    with pytest.raises(lib().KtupError) as err:
+        rec_launch(c, dev, b, -1.0, 1.0, 1, gnorm=ws)
+    assert err.value.code == lib().ERR_UNSUPPORTED
+    assert float(ws.abs().max()) == 0.0 and all(v is None or float(v.abs().max()) == 0.0 for v in b.values())
+
+
+# ---------------------------------------------------------------------------------------------------- stored rows
+def rows_launch(c, dev, out, target, gscale, orth, share=False, cols=None, small_ws=None, n_slots=4):
+    """ktup_train_rec_step_rows (small_ws None) or _rows_ws.  share: gR / gRn NULL.  cols: (u, i, neg, cursor, n_batches) id columns."""
+    kt = c['ktup']
+    u_ids, i_ids, neg, cursor, n_batches = (dev['u2'], dev['i2'], None, None, 0) if cols is None else cols
+    args = [p(dev['U']), c['ldu'], p(dev['I']), c['ldi'], p(dev['E']), c['lde'] if kt else 0, p(dev['i2e']), c['ne'] if kt else -1, p(dev['P']),
+            p(dev['Pn']), p(dev['R']), p(dev['Rn']), c['d'], c['n_pref'], c['d'], p(u_ids), p(i_ids), c['B'], int(c['l1']), float(target),
+            float(gscale), int(orth), p(out['loss']), p(out['GU']), p(out['GV']), p(out['P']), p(out['Pn']),
+            None if share else p(out['R']), None if share else p(out['Rn']), p(out['sumsq']), n_slots, p(neg), p(cursor), n_batches,
+            GUMBEL_INPUT if c['hard'] else GUMBEL_OFF, p(dev['uni'])]
+    if small_ws is None:
+        lib().call('ktup_train_rec_step_rows', *args, None)
+    else:
+        lib().call('ktup_train_rec_step_rows_ws', *args, p(small_ws), small_ws.numel() * 4, None)
+    torch.cuda.synchronize()
+
+
+def rows_buffers(c, n_slots=4):
+    d, P, B = c['d'], c['n_pref'], c['B']
+    out = {'loss': torch.zeros(2, device=DEV), 'GU': torch.full((B, d), SENTINEL, device=DEV), 'GV': torch.full((2 * B, d), SENTINEL, device=DEV),
+           'P': torch.zeros(P, d, device=DEV), 'Pn': torch.zeros(P, d, device=DEV), 'R': None, 'Rn': None,
+           'sumsq': torch.zeros(n_slots, dtype=torch.float64, device=DEV)}
+    if c['ktup']:
+        out.update(R=torch.zeros(P, d, device=DEV), Rn=torch.zeros(P, d, device=DEV))
+    return out
+
+
+def rows_compare(c, out, loss, want, sumsq, small=('P', 'Pn', 'R', 'Rn')):
+    close_loss(out['loss'], loss)
+    for k in ('GU', 'GV') + tuple(small):
+        if k in want:
+            close_grad(out[k], want[k], k)
+    close_sum(float(out['sumsq'].sum()), sumsq, 'sumsq')
+
+
+@pytest.mark.parametrize('hard', [False, True])
+@pytest.mark.parametrize('ktup', [False, True])
+@pytest.mark.parametrize('P', [4, 20])
+@pytest.mark.parametrize('d', DS)
+def test_rec_rows(d, P, ktup, hard):
+    """GU / GV are STORED (the buffers start at a sentinel), the small tables' gradients accumulated, sumsq as the header defines it."""
+    for B in (5, 13):
+        l1 = B == 5
+        c = R.rec_case(d, P, B, ktup, hard, l1, seed_of(d, P, ktup, hard, B, 13), family='rec rows')
+        dev = rec_device(c)
+        loss, want, sumsq = R.rec_rows_reference(c, -1.0, 0.5, 1)
+        out = rows_buffers(c)
+        rows_launch(c, dev, out, -1.0, 0.5, 1)
+        rows_compare(c, out, loss, want, sumsq)
+        # replicas of the small tables' gradients: gP / gPn receive the orth gradient alone, the replica sum holds the rest
+        loss0, want0, _ = R.rec_rows_reference(c, -1.0, 0.5, 0)
+        n_bytes = lib().load().ktup_train_rec_step_rows_ws_bytes(B, P, d)
+        assert n_bytes == 8 * 2 * P * d * 4
+        ws = torch.zeros(n_bytes // 4, device=DEV)
+        out = rows_buffers(c)
+        rows_launch(c, dev, out, -1.0, 0.5, 1, small_ws=ws)
+        rows_compare(c, out, loss, want, sumsq, small=())
+        close_grad(out['P'], want['P'] - want0['P'], 'P (orth alone)')
+        close_grad(out['Pn'], want['Pn'] - want0['Pn'], 'Pn (orth alone)')
+        rep = ws.view(8, 2, P, d).sum(0)
+        close_grad(rep[0], want0['P'], 'replicas A')
+        close_grad(rep[1], want0['Pn'], 'replicas C')
+        if ktup:
+            assert float(out['R'].abs().max()) == 0.0 and float(out['Rn'].abs().max()) == 0.0
+            # gR == NULL: gP / gPn are the gradients of both summands (orth then needs separate gradients: off)
+            out = rows_buffers(c)
+            rows_launch(c, dev, out, -1.0, 0.5, 0, share=True)
+            _, _, sumsq0 = R.rec_rows_reference(c, -1.0, 0.5, 0)
+            rows_compare(c, out, loss0, want0, sumsq0, small=('P', 'Pn'))
+            assert float(out['R'].abs().max()) == 0.0 and float(out['Rn'].abs().max()) == 0.0
+        if not hard:
+            # id columns of three batches; the kernel reads batch (cursor mod 3) = 1 itself
+            gen = torch.Generator().manual_seed(B)
+            cu, ci, cn = (torch.randint(0, n, (3, B), generator=gen) for n in (c['nu'], c['nitems'], c['nitems']))
+            cu[1], ci[1], cn[1] = c['u'], c['pi'], c['ni']
+            cols = (cu.to(DEV), ci.to(DEV), cn.to(DEV), torch.tensor([7], dtype=torch.int64, device=DEV), 3)
+            out = rows_buffers(c, n_slots=1)
+            rows_launch(c, dev, out, -1.0, 0.5, 1, cols=cols, n_slots=1)
+            rows_compare(c, out, loss, want, sumsq)
+
+
+@pytest.mark.parametrize('d', [64, 100, 256])
+def test_rec_reg_rows(d):
+    """TUP's row regularisers on top of nonzero GU / GV / gP, with different scales for the rows and for pref; the rows lie on both
+    sides of norm 1 (0.64 and 1.5625, asserted by the case construction)."""
+    B, P = 13, 20
+    c = R.rec_case(d, P, B, False, False, False, seed_of(d, 14), pitch=(4, 12, 0), family='rec rows')
+    gen = torch.Generator().manual_seed(d)
+    GU0, GV0, gP0 = torch.randn(B, d, generator=gen), torch.randn(2 * B, d, generator=gen), torch.randn(P, d, generator=gen)
+    loss, GU, GV, gP = R.reg_rows_reference(c, GU0.double(), GV0.double(), gP0.double(), 0.5, 0.125)
+    assert loss[0] > 0.0 and loss[1] > 0.0
+    dev = rec_device(c)
+    out_loss, dGU, dGV, dgP = torch.zeros(2, device=DEV), GU0.to(DEV), GV0.to(DEV), gP0.to(DEV)
+    lib().call('ktup_train_rec_reg_rows', p(dev['U']), c['ldu'], p(dev['I']), c['ldi'], d, p(dev['u2']), p(dev['i2']), B, p(dGU), p(dGV),
+               p(dev['P']), P, p(dgP), 0.5, 0.125, p(out_loss), None)
+    torch.cuda.synchronize()
+    close_loss(out_loss, loss)
+    close_grad(dGU, GU, 'GU')
+    close_grad(dGV, GV, 'GV')
+    close_grad(dgP, gP, 'gP')
+    small = (c['U'][:, :d].double() ** 2).sum(1)[c['u']] < 1.0      # rows below norm 1 are left as they were, exactly
+    assert bool(small.any()) and torch.equal(dGU.cpu()[small], GU0[small])
+
+
+# ==================================================================================================== kg step
+def kg_device(c):
+    dev = {k: c[k].to(DEV) for k in ('E', 'R')}
+    dev['N'] = c['N'].to(DEV) if c['transh'] else None
+    dev['h2'], dev['t2'] = torch.cat([c['h'], c['nh']]).to(DEV), torch.cat([c['t'], c['nt']]).to(DEV)
+    dev['r2'] = torch.cat([c['r'], c['r']]).to(DEV)
+    return dev
+
+
+def kg_buffers(c):
+    return {'loss': torch.zeros(4, device=DEV), 'E': torch.zeros(c['ne'], c['lde'], device=DEV), 'R': torch.zeros(c['nr'], c['ldr'], device=DEV),
+            'N': torch.zeros(c['nr'], c['ldn'], device=DEV) if c['transh'] else None}
+
+
+def kg_launch(c, dev, b, margin, gscale, regs, gnorm=None):
+    th = c['transh']
+    lib().call('ktup_train_kg_step', int(th), p(dev['E']), c['lde'], p(dev['R']), c['ldr'], p(dev['N']), c['ldn'] if th else 0, c['d'],
+               p(dev['h2']), p(dev['t2']), p(dev['r2']), c['B'], int(c['l1']), float(margin), float(gscale), int(regs), p(b['loss']), p(b['E']),
+               p(b['R']), p(b['N']), p(gnorm), None)
+    torch.cuda.synchronize()
+
+
+def kg_compare(c, b, loss, want, times=1):
+    d = c['d']
+    close_loss(b['loss'], [times * x for x in loss])
+    for k in ('E', 'R', 'N'):
+        if b[k] is None:
+            continue
+        close_grad(b[k][:, :d], times * want[k], k)
+        if b[k].shape[1] > d:
+            assert float(b[k][:, d:].abs().max()) == 0.0
+    untouched_rows_are_zero(b['E'], c['ne'], torch.cat([c['h'], c['t'], c['nh'], c['nt']]))
+    untouched_rows_are_zero(b['R'], c['nr'], c['r'])
+    if b['N'] is not None:
+        untouched_rows_are_zero(b['N'], c['nr'], c['r'])
+
+
+def kg_check(c, margin=1.0, gscale=0.5, regs=7, times=1):
+    loss, want = R.kg_reference(c, margin, gscale, regs)
+    dev, b = kg_device(c), kg_buffers(c)
+    for _ in range(times):
+        kg_launch(c, dev, b, margin, gscale, regs)
+    kg_compare(c, b, loss, want, times)
+    return b
+
+
+MODELS = [(False, False), (False, True), (True, False), (True, True)]       # (transh, l1)
+
+
+@pytest.mark.parametrize('B', [1, 3, 4, 5, 16, 17, 67])
+@pytest.mark.parametrize('d', [4, 20, 36, 64, 100, 128, 132, 256])
+def test_kg_step_shapes(d, B):
+    """All three lane-group widths (16 lanes up to d = 64, 32 up to 128, 64 beyond), each with idle lanes (d = 4, 20, 36; 100; 132);
+    B below, at and above the 16 / 8 / 4 triples of a workgroup."""
+    for transh, l1 in MODELS:
+        kg_check(R.kg_case(d, B, transh, l1, seed_of(d, B, transh, l1, 20), family='kg shapes'))
+
+
+@pytest.mark.parametrize('margin', [1.0, 0.3])
+@pytest.mark.parametrize('regs', [0, 1, 2, 4, 7])
+def test_kg_step_regs_and_margin(regs, margin):
+    for d in (36, 100):
+        for transh, l1 in MODELS:
+            kg_check(R.kg_case(d, 17, transh, l1, seed_of(d, transh, l1, 21), margins=(1.0, 0.3), family='kg regs'), margin, 0.5, regs)
+
+
+@pytest.mark.parametrize('transh,l1', MODELS)
+def test_kg_step_options(transh, l1):
+    """Padded pitches (E, R and N each their own) and two launches into the same buffers."""
+    for d in (20, 100, 132):
+        c = R.kg_case(d, 17, transh, l1, seed_of(d, transh, l1, 22), pitch=(4, 12, 8), family='kg options')
+        kg_check(c)
+        kg_check(c, times=2)
+
+
+@pytest.mark.parametrize('transh', [False, True])
+@pytest.mark.parametrize('d', [36, 100, 256])
+def test_kg_step_exact_zero(d, transh):
+    """A triple (e, r0, e) with an all-zero relation row: z is exactly 0, torch's sign(0) is 0, and the entity -- which no other
+    triple uses -- gets EXACTLY no gradient although the triple is active."""
+    c = R.kg_exact_zero_case(d, transh, True, seed_of(d, transh, 23))
+    b = kg_check(c, 1.0, 0.5, 0)
+    assert float(b['E'][c['zero_entity']].abs().max()) == 0.0
+    assert float(b['E'][c['zero_entity'] + 1].abs().max()) > 0.0
+
+
+@pytest.mark.parametrize('transh,l1', MODELS)
+@pytest.mark.parametrize('d', [20, 100, 256])
+def test_kg_step_tracked_norm(d, transh, l1):
+    """B = 67 on 9 entities and 4 relations: every row is shared many times; the tracked sum is held to the REFERENCE's gradients."""
+    c = R.kg_case(d, 67, transh, l1, seed_of(d, transh, l1, 24), family='kg norm')
+    loss, want = R.kg_reference(c, 1.0, 0.5, 7)
+    dev, b = kg_device(c), kg_buffers(c)
+    ws = torch.zeros(64, dtype=torch.float64, device=DEV)
+    kg_launch(c, dev, b, 1.0, 0.5, 7, gnorm=ws)
+    kg_compare(c, b, loss, want)
+    close_sum(tracked_norm(ws), float(sum((g ** 2).sum() for g in want.values())), 'tracked squared norm')
+
+
+@pytest.mark.parametrize('d,B', [(256, 4099), (100, 8195), (64, 16387)])
+def test_kg_step_grid_stride(d, B):
+    """At most 1024 workgroups of 4 / 8 / 16 triples: three triples more than they hold in one pass, so that workgroup 0 walks two.
+    Tables of 3000 entities and 40 relations."""
+    for transh, l1 in ((True, True), (False, False)):
+        kg_check(R.kg_case(d, B, transh, l1, seed_of(d, transh, 25), ne=3000, nr=40, family='kg stride'))
+
+
+@pytest.mark.parametrize('transh,l1', MODELS)
+def test_kg_step_deterministic(transh, l1):
+    with option('deterministic', 1):
+        for d in (36, 100, 256):
+            kg_check(R.kg_case(d, 67, transh, l1, seed_of(d, transh, l1, 26), family='kg stride'))
+
+
+@pytest.mark.parametrize('mark', ['minus one', 'ent_pad'])
+@pytest.mark.parametrize('ordered', [False, True])
+@pytest.mark.parametrize('transh,l1', MODELS)
+@pytest.mark.parametrize('d', [36, 100, 256])
+def test_kg_rows(d, transh, l1, ordered, mark):
+    """ktup_train_kg_step_rows: the 4B entity-row gradients STORED (the buffer starts at a sentinel and a twin's kept end, marked -1
+    or ent_pad, stays unwritten: its gradient is in the positive's row), gR / gN accumulated, with and without the relation order."""
+    B = 17
+    c = R.kg_case(d, B, transh, l1, seed_of(d, transh, l1, 27), family='kg rows')
+    loss, GE, written, small, sumsq = R.kg_rows_reference(c, 1.0, 0.5, 7)
+    dev, b = kg_device(c), kg_buffers(c)
+    pad = c['ne'] + 5                                               # an id no row has
+    ent = R.kg_rows_ids(c, -1 if mark == 'minus one' else pad).to(DEV)
+    order = None
+    if ordered:
+        order = torch.full((B,), -1, dtype=torch.int32, device=DEV)
+        lib().call('ktup_shard_kg_rel_order', p(dev['r2']), B, c['nr'], p(order), None)
+        torch.cuda.synchronize()
+        assert sorted(order.cpu().tolist()) == list(range(B))
+        assert bool((c['r'][order.cpu().long()].diff() >= 0).all())
+    dGE = torch.full((4 * B, d), SENTINEL, device=DEV)
+    ss = torch.zeros(4, dtype=torch.float64, device=DEV)
+    th = c['transh']
+    lib().call('ktup_train_kg_step_rows', int(th), p(dev['E']), c['lde'], p(dev['R']), c['ldr'], p(dev['N']), c['ldn'] if th else 0, d, p(ent), pad,
+               p(dev['r2']), p(order), B, int(l1), 1.0, 0.5, 7, p(b['loss']), p(dGE), p(b['R']), p(b['N']), p(ss), 4, None)
+    torch.cuda.synchronize()
+    close_loss(b['loss'], loss)
+    host = dGE.cpu()
+    assert bool((host[~written] == SENTINEL).all())
+    close_grad(host[written], GE[written], 'GE')
+    close_grad(b['R'], small['R'], 'R')
+    if th:
+        close_grad(b['N'], small['N'], 'N')
+    close_sum(float(ss.sum()), sumsq, 'sumsq')
+
+
+def test_redraw_counts_stay_small():
+    """The case generator's conditions are asserted before any launch.  Independent of which tests ran before it in this process,
+    this one draws the most demanding case of every family itself -- the hard gate at P = 32, L1, the 16387-triple batch, the
+    smallest batch that must hold active and inactive triples, two margins, the exact zero -- and prints and bounds what they
+    needed: seeds (whole cases drawn again; the issue's handful) and inner rounds (offending gate rows / triples drawn again while
+    a case is built: the hinge band holds ~1 triple in 250, so 16387 triples clear in two or three rounds; a batch that lacks an
+    active or an inactive triple gets one planted in one).  The counts of the cases the other tests of this process drew are
+    in the same tables."""
+    for d in DS:
+        R.rec_case(d, 20 if d == 256 else 32, 67, True, True, True, seed_of(d, 30), family='counts: rec')
+    R.rec_case(100, 20, 2061, False, True, True, seed_of(31), sizes=BIG, family='counts: rec stride')
+    for transh, l1 in MODELS:
+        for B in (4, 5, 17, 67):
+            R.kg_case(100, B, transh, l1, seed_of(B, transh, l1, 32), margins=(1.0, 0.3), family='counts: kg')
+        R.kg_case(64, 16387, transh, l1, seed_of(transh, l1, 33), ne=3000, nr=40, family='counts: kg stride')
+    R.kg_exact_zero_case(100, True, True, seed_of(34))
+    print('seeds needed per family:', R.DRAWS)
+    print('inner rounds per family:', R.ROUNDS)
+    assert max(R.DRAWS.values()) <= 6
+    assert max(R.ROUNDS.values()) <= 5
