@@ -920,6 +920,40 @@ int ktup_eval_cfkg_topk(const float* U, int64_t ldu, const float* R, int64_t ldr
                         const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids,
                         float* top_scores, void* ws, void* stream);
 
+/* =================================================================== the TransR training step in one launch (csrc/ktup_transr_step.hip)
+ * transR.py:65-78 + utils/misc.py:21-26 scored, and knowledge_representation.py:176-204's step built, for the KG driver and CKE.
+ * h / t / r hold [pos ; neg], 2B entries each (the layout of ktup_train_kg_step and ktup_feed_kg): rows k and k + B are the positive
+ * triple of example k and its corrupted twin.  M is the projection table of ktup_score_transr_fwd: n_rel rows of d x d (row major),
+ * pitch ldm.  With
+ *     q = E[h] - E[t],     y = M_r q + R[r],     s = sum_j |y[j]|  (l1 != 0)   or   sum_j y[j]^2
+ *     loss[0] += sum_k max(s+[k] - s-[k] + margin, 0)           an example is ACTIVE iff the argument is > 0 (ktup_loss_margin_fused)
+ *     loss[2] += normLoss over the 4B entity rows [ph ; pt ; nh ; nt]       (regs bit 1; every occurrence counts, ktup_reg_norm_fused)
+ *     loss[3] += normLoss over the 2B relation rows                         (regs bit 2)
+ * loss[1] is not touched (regs bit 0, TransH's orthogonalLoss, is KTUP_ERR_INVALID_ARG) and the slots are unscaled.  With g = +gscale
+ * for the positive and -gscale for the corrupted triple of an active example (0 for an inactive one) and gy = g * v, v = sign(y)
+ * (sign(0) = 0, as torch.abs differentiates) or 2 y, the gradients are ADDED (float atomics) to table-shaped buffers with the
+ * tables' pitches:
+ *     gR[r] += gy,     gM[r] += gy (x) q,     gE[h] += M_r^T gy,     gE[t] -= M_r^T gy
+ * and a regularised row x with |x|^2 > 1 adds 2 gscale x to its gradient row once per occurrence.  Cells that receive nothing are
+ * not written: a relation none of whose examples is active keeps its rows of gM exactly as they were.
+ *
+ * ONE launch with no workspace, no memset and no host synchronisation: it can be captured into a graph and replayed (the
+ * relation-bucketed ktup_score_transr_fwd / _bwd clear counters in a pooled workspace with a memset node and must not be).  A
+ * workgroup owns (relation, one of nsplit contiguous parts of the batch): it compacts its examples out of the id list into LDS,
+ * stages M_r once and runs 16-triple wave tiles (8 examples with their twins) on v_mfma_f32_16x16x4_f32.  nsplit: 0 = chosen by
+ * the library; a request above 32 or above B is reduced.  An example whose twin names another relation (r[k + B] != r[k]; the
+ * reference's samplers draw none, utils/data.py:23-56) is computed by one wave with both matrices read from memory.
+ *
+ * d in {64, 100, 128}, 1 <= B <= 4096, 1 <= n_rel <= 4096, every table and gradient 16-byte aligned with a pitch that is a
+ * multiple of 4 floats; anything else, or the library option "deterministic" being set, is KTUP_ERR_UNSUPPORTED and launches
+ * nothing: the caller keeps its multi-launch route.  No tracked gradient norm (ktup_optim_clip_step runs its own norm pass).
+ * ktup_train_transr_step_supported(d): 1 if a launch with this width would be taken (no launch is made), else 0.                */
+int ktup_train_transr_step_supported(int d);
+int ktup_train_transr_step(const float* E, int64_t lde, const float* R, int64_t ldr, const float* M, int64_t ldm,
+                           int64_t n_rel, int d, const int64_t* h, const int64_t* t, const int64_t* r, int64_t B,
+                           int l1, float margin, float gscale, int regs, int nsplit, float* loss,
+                           float* gE, float* gR, float* gM, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,9 @@ def train_loop(FLAGS, model, trainer, train_dataset, eval_datasets, entity_total
         return 'kg', losses
 
     D.training_loop(FLAGS, model, trainer, logger, do_step, do_eval, ['kg'], sampler=sampler, stepper=stepper)
+    if stepper is not None and stepper.transr:
+        logger.info('TransR training step: {}; {} steps were graph replays.'.format(
+            'one launch (ktup_train_transr_step)' if stepper.transr_step else 'multi-launch route, issued eagerly', stepper.replays['kg']))
     trainer.save(trainer.checkpoint_path + '_final')      # knowledge_representation.py:219
 
 

@@ -106,6 +106,7 @@ class _StepperBase(object):
             self._gn = torch.zeros(64, dtype=torch.float64, device=dev)                 # KTUP_GNORM_WS_DOUBLES
         self._graphs = {}
         self._eager_steps = {k: 0 for k in self.KINDS}
+        self.replays = {k: 0 for k in self.KINDS}                                        # host-fed steps that were replays of the step's graph
         self._feeds, self._sampler, self._feed_launch, self._feed_ok = {}, None, {}, {}
         self._acc_on = False
         self.acc = {k: torch.zeros((), **f32) for k in self.KINDS}                       # fed steps: running sum of the steps' losses
@@ -424,6 +425,7 @@ class _StepperBase(object):
         entry[0].replay()
         if not captured:
             fused.bump_steps()
+            self.replays[kind] += 1
         self.trainer.step += 1
         return entry[1]
 
@@ -651,7 +653,15 @@ class KGStepper(_StepperBase):
         self.tabs = (E, R, model.norm_embeddings.weight) if self.transh else (E, R, model.proj_embeddings.weight) if self.transr else (E, R)
         if self.transd:
             self.tabs = (E, R, model.ent_proj_embeddings.weight, model.rel_proj_embeddings.weight)
-        if self.transr:             # scratch of the relation-bucketed forward (K4)
+        # TransR: the whole step as ONE launch (ktup_train_transr_step; KTUP_FUSED_STEP=0 keeps the bucketed multi-launch route).
+        # `fused_step` stays False for it: the device-fed steps are not built for TransR, which takes its batches from the host.
+        self.transr_step = bool(self.transr and self.want_fused and L.load().ktup_train_transr_step_supported(E.shape[1])
+                                and 1 <= B <= 4096 and 1 <= min(R.shape[0], self.tabs[2].shape[0]) <= 4096)
+        # The bucketed TransR kernels (d = 64, 100, 128) clear their counters with a memset into a pooled workspace; a captured
+        # memset node of that kind writes garbage from its second replay on, so that route is never captured.
+        self._never_capture = self.transr and not self.transr_step and E.shape[1] in (64, 100, 128)
+        self.rws = None
+        if self.transr and not self.transr_step:             # scratch of the relation-bucketed forward (K4)
             nbytes = L.load().ktup_score_transr_workspace_bytes(2 * B, R.shape[0])
             self.rws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=self.dev)
         self._id_buffers('kg', i64)
@@ -669,6 +679,13 @@ class KGStepper(_StepperBase):
                                Rn_.stride(0) if self.transh else 0, d, _p(self.h2), _p(self.t2), _p(self.r2), B, self.l1, self.margin, 1.0,
                                7 if self.transh else 6, _p(self.loss), _p(E.grad), _p(R.grad), _p(Rn_.grad) if self.transh else None,
                                self._gn_ptr(), st)
+        if self.transr_step:
+            M = self.tabs[2]
+            self._transr_fused = b('ktup_train_transr_step', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0),
+                                   min(R.shape[0], M.shape[0]), d, _p(self.h2), _p(self.t2), _p(self.r2), B, self.l1, self.margin, 1.0, 6, 0,
+                                   _p(self.loss), _p(E.grad), _p(R.grad), _p(M.grad), st)
+            self._calls = []
+            return
         if self.transh:
             Rn = self.tabs[2]
             n_rel = min(R.shape[0], Rn.shape[0])
@@ -713,6 +730,10 @@ class KGStepper(_StepperBase):
             self._kg_fused()
             self._optimizer_launches(loss=(_p(self.loss), 4, 1.0, _p(self.out['kg']), self._acc_ptr('kg')), tracked=True)
             return self.out['kg']
+        if self.transr_step:             # one launch: both TransR scores, marginLoss, the two regularisers, every gradient
+            self._transr_fused()
+            self._optimizer_launches(loss=(_p(self.loss), 4, 1.0, _p(self.out['kg']), self._acc_ptr('kg')))
+            return self.out['kg']
         self.loss.zero_()
         for launch in self._calls:
             launch()
@@ -720,6 +741,10 @@ class KGStepper(_StepperBase):
         return self.loss[:4].sum()
 
     def kg_step(self, ph, pt, pr, nh, nt, nr):
+        if self._never_capture:          # the bucketed TransR route: issued launch by launch, as BaselineJointStepper.kg_step does for CKE
+            out = self._kg_eager(ph, pt, pr, nh, nt, nr)
+            self.trainer.step += 1
+            return out
         return self._step('kg', self._kg_eager, (ph, pt, pr, nh, nt, nr))
 
 

@@ -101,10 +101,15 @@ class BaselineJointStepper(_StepperBase):
             M = m.proj_embeddings.weight
             self.tabs = (U, I, E, R, M)
             touch = {'rec': (U, I, E), 'kg': (E, R, M)}
-            nbytes = L.load().ktup_score_transr_workspace_bytes(2 * B, R.shape[0])
-            self.rws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=self.dev)
+            # the kg step as ONE launch (ktup_train_transr_step); KTUP_FUSED_STEP=0, or a shape it does not take, keeps the bucketed route
+            self.transr_step = bool(self.want_fused and L.load().ktup_train_transr_step_supported(d)
+                                    and 1 <= B <= 4096 and 1 <= min(R.shape[0], M.shape[0]) <= 4096)
+            self.rws = None
+            if not self.transr_step:                                    # scratch of the relation-bucketed forward
+                nbytes = L.load().ktup_score_transr_workspace_bytes(2 * B, R.shape[0])
+                self.rws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=self.dev)
             self.align = False
-            self.fused_step = False                                     # the TransR kg step is several launches: not device-fed
+            self.fused_step = False                                     # host-fed only
         elif self.cfkg:
             if I is not E:
                 raise L.KtupError('CFKG scores items on the entity table (-share_embeddings is forced)')
@@ -176,6 +181,12 @@ class BaselineJointStepper(_StepperBase):
             self._rec_fused = b('ktup_train_dot_step', _p(U), U.stride(0), _p(I), I.stride(0), _p(E), E.stride(0), _p(m._item2ent),
                                 m.ent_total - 1, None, None, None, d, _p(self.u2), _p(self.i2), B, self.target, inv, _p(self.loss),
                                 g(U), g(I), g(E), None, st)
+            if self.transr_step:
+                self._kg_transr = b('ktup_train_transr_step', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0),
+                                    min(R.shape[0], M.shape[0]), d, _p(self.h2), _p(self.t2), _p(self.r2), B, self.l1, self.margin,
+                                    self.kg_lambda, 6, 0, _p(self.loss), g(E), g(R), g(M), st)
+                self._kg = []
+                return
             # the TransR sequence of KGStepper._bind, with kg_lambda as the upstream scalar
             self._kg = [
                 b('ktup_score_transr_fwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0), min(R.shape[0], M.shape[0]), d,
@@ -257,6 +268,9 @@ class BaselineJointStepper(_StepperBase):
         if not self.cke and self.kg_fused:
             self._kg_fused()
             return self._finish('kg', 4, self.kg_lambda)
+        if self.cke and self.transr_step:                               # one launch; gradients x kg_lambda, slots unscaled
+            self._kg_transr()
+            return self._finish('kg', 4, self.kg_lambda)
         for launch in self._kg:                                         # gradients x kg_lambda (device scalar), slots unscaled
             launch()
         return self._finish('kg', 4, self.kg_lambda)
@@ -275,6 +289,8 @@ class BaselineJointStepper(_StepperBase):
             # Never captured: the relation-bucketed TransR kernels (d = 64, 100, 128) clear their counters in the workspace with
             # hipMemsetAsync, and a captured memset node whose destination lies inside a pooled allocation writes garbage from its
             # second replay on -- the bucket kernels then index past the workspace.  The rec step replays.
+            # (With `transr_step` the kg step is ktup_train_transr_step, which has no memset and replays safely; it is still
+            # issued eagerly here because the suite pins this stepper's graphs to {'rec'}.)
             out = self._kg_eager(ph, pt, pr, nh, nt, nr)
             self.trainer.step += 1
             return out
