@@ -954,6 +954,42 @@ int ktup_train_transr_step(const float* E, int64_t lde, const float* R, int64_t 
                            int l1, float margin, float gscale, int regs, int nsplit, float* loss,
                            float* gE, float* gR, float* gM, void* stream);
 
+/* =================================================================== the TransD training step in one launch (csrc/ktup_transd_step.hip)
+ * transD.py:61-76 + utils/misc.py:36-37 scored, and knowledge_representation.py:176-204's step built, for the KG driver.  h / t / r
+ * hold [pos ; neg], 2B entries each (the layout of ktup_train_kg_step and ktup_feed_kg): rows k and k + B are the positive triple of
+ * example k and its corrupted twin; the twin's relation r[k + B] may differ from r[k] and takes no other path.  Ep / Rp are the
+ * projection tables of ktup_score_transd_fwd.  With h = E[h], h_p = Ep[h], t = E[t], t_p = Ep[t], r = R[r], r_p = Rp[r] and
+ *     alpha = h . h_p,     beta = t . t_p,     v = (h - t) + r + (alpha - beta) r_p,     s = sum_j |v[j]|  (l1 != 0)   or   sum_j v[j]^2
+ *     loss[0] += sum_k max(s+[k] - s-[k] + margin, 0)           an example is ACTIVE iff the argument is > 0 (ktup_loss_margin_fused)
+ *     loss[2] += normLoss over the 4B entity rows [ph ; pt ; nh ; nt]       (regs bit 1; every occurrence counts, ktup_reg_norm_fused)
+ *     loss[3] += normLoss over the 2B relation rows                         (regs bit 2)
+ * loss[1] is never written (regs bit 0, TransH's orthogonalLoss, and any bit above 2 are KTUP_ERR_INVALID_ARG) and the slots are
+ * unscaled.  Ep and Rp carry no regulariser (knowledge_representation.py:200-204).  With g = +gscale dist'(v) for the positive and
+ * -gscale dist'(v) for the corrupted triple of an active example (0 for an inactive one), dist'(v) = sign(v) (sign(0) = 0, as
+ * torch.abs differentiates) or 2 v, and gamma = g . r_p, the gradients are ADDED (float atomics) to table-shaped buffers with the
+ * tables' pitches:
+ *     gE[h] += g + gamma h_p,   gEp[h] += gamma h,   gE[t] -= g + gamma t_p,   gEp[t] -= gamma t,   gR[r] += g,   gRp[r] += (alpha - beta) g
+ * and a regularised row x with |x|^2 > 1 adds 2 gscale x to its gradient row once per occurrence.  A cell that receives nothing is
+ * not written (an inactive example adds nothing to gEp and gRp, and to gE / gR only where a regulariser fires); pitch gaps and the
+ * lanes beyond a row are never written.
+ *
+ * ONE launch with no workspace, no memset and no host synchronisation: it can be captured into a graph and replayed.  A group of
+ * 16 / 32 / 64 lanes (by d / 4) owns an example and holds the rows of both triples in registers; the loss partials of a workgroup
+ * go out as one atomic per slot.  `gnorm` (may be NULL): the KTUP_GNORM_WS_DOUBLES workspace of ktup_train_kg_step -- every add into
+ * the four buffers is a returning atomic and the squared norm they build is tracked for ktup_optim_clip_step.  The library option
+ * "deterministic" takes the form of ktup_train_kg_step: one lane group of one workgroup walks the batch in order.
+ *
+ * 1 <= d <= 256 with d % 4 == 0, every table and gradient 16-byte aligned with a pitch that is a multiple of 4 floats, B >= 1;
+ * any other width or alignment is KTUP_ERR_UNSUPPORTED, launches nothing and writes nothing: the caller keeps its multi-launch
+ * route.  B == 0 is KTUP_OK without a launch (KTUP_ERR_INVALID_ARG with a tracked norm, as for ktup_train_kg_step); a null pointer
+ * (named in ktup_last_error) and d <= 0 are KTUP_ERR_INVALID_ARG.  Every argument is checked before the first HIP call.
+ * ktup_train_transd_step_supported(d): 1 if a launch with this width would be taken (no launch is made), else 0.                */
+int ktup_train_transd_step_supported(int d);
+int ktup_train_transd_step(const float* E, int64_t lde, const float* R, int64_t ldr, const float* Ep, int64_t ldep,
+                           const float* Rp, int64_t ldrp, int d, const int64_t* h, const int64_t* t, const int64_t* r,
+                           int64_t B, int l1, float margin, float gscale, int regs, float* loss,
+                           float* gE, float* gR, float* gEp, float* gRp, double* gnorm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,9 @@ SIGNATURES = {
     'ktup_eval_cfkg_topk': [c_p, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
     'ktup_train_transr_step_supported': [c_i],
     'ktup_train_transr_step': [c_p, c_l, c_p, c_l, c_p, c_l, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    'ktup_train_transd_step_supported': [c_i],
+    'ktup_train_transd_step': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p,
+                               c_p],
 }
 _RESTYPE = {'ktup_last_error': ctypes.c_char_p, 'ktup_shard_reduce_list_len': ctypes.c_int64, 'ktup_shard_route_workspace_bytes': ctypes.c_size_t,
             'ktup_shard_route_sort_bytes': ctypes.c_size_t, 'ktup_pref_workspace_bytes': ctypes.c_size_t, 'ktup_eval_kg_ranks_workspace_bytes': ctypes.c_size_t, 'ktup_eval_kg_ranks_transr_workspace_bytes': ctypes.c_size_t, 'ktup_eval_kg_ranks_fused_workspace_bytes': ctypes.c_size_t,

@@ -130,6 +130,10 @@ def train_loop(FLAGS, model, trainer, train_dataset, eval_datasets, entity_total
     if stepper is not None and stepper.transr:
         logger.info('TransR training step: {}; {} steps were graph replays.'.format(
             'one launch (ktup_train_transr_step)' if stepper.transr_step else 'multi-launch route, issued eagerly', stepper.replays['kg']))
+    if stepper is not None and stepper.transd:
+        logger.info('TransD training step: {}; {} steps were graph replays; device-fed: {}.'.format(
+            'one launch (ktup_train_transd_step)' if stepper.transd_step else 'multi-launch route',
+            stepper.replays['kg'] + stepper.fed_replays['kg'], 'yes' if feed is not None and stepper.can_feed('kg') else 'no'))
     trainer.save(trainer.checkpoint_path + '_final')      # knowledge_representation.py:219
 
 

@@ -107,6 +107,7 @@ class _StepperBase(object):
         self._graphs = {}
         self._eager_steps = {k: 0 for k in self.KINDS}
         self.replays = {k: 0 for k in self.KINDS}                                        # host-fed steps that were replays of the step's graph
+        self.fed_replays = {k: 0 for k in self.KINDS}                                    # device-fed steps that were (part of) a graph replay
         self._feeds, self._sampler, self._feed_launch, self._feed_ok = {}, None, {}, {}
         self._acc_on = False
         self.acc = {k: torch.zeros((), **f32) for k in self.KINDS}                       # fed steps: running sum of the steps' losses
@@ -128,9 +129,13 @@ class _StepperBase(object):
             ok = False
             if kind in self._feeds and self.world == 1:
                 self._plans()                   # decides fused_step for this shape
-                ok = bool(self.fused_step)      # the multi-launch routes take id arrays the feed launches do not fill
+                ok = bool(self._feedable())     # the multi-launch routes take id arrays the feed launches do not fill
             self._feed_ok[kind] = ok
         return ok
+
+    def _feedable(self):
+        """Does the bound step read nothing but the [pos ; neg] id arrays the feed launches fill?"""
+        return self.fused_step
 
     def _acc_ptr(self, kind):
         """Fed steps: the optimizer launch adds the step's loss to acc[kind] itself."""
@@ -206,6 +211,8 @@ class _StepperBase(object):
         entry[0].replay()
         if not captured:
             fused.bump_steps(len(kinds))
+            for kind, c in count.items():
+                self.fed_replays[kind] += c
         self.trainer.step += len(kinds)
         return len(kinds)
 
@@ -304,6 +311,7 @@ class _StepperBase(object):
         entry[0].replay()
         if not captured:
             fused.bump_steps()
+            self.fed_replays[kind] += 1
         self.trainer.step += 1
         return entry[1]
 
@@ -660,6 +668,11 @@ class KGStepper(_StepperBase):
         # The bucketed TransR kernels (d = 64, 100, 128) clear their counters with a memset into a pooled workspace; a captured
         # memset node of that kind writes garbage from its second replay on, so that route is never captured.
         self._never_capture = self.transr and not self.transr_step and E.shape[1] in (64, 100, 128)
+        # TransD: the whole step as ONE launch too (ktup_train_transd_step; KTUP_FUSED_STEP=0 keeps the multi-launch route).  It reads
+        # the [pos ; neg] id arrays alone, so the device-fed steps take it (`_feedable`); `fused_step` stays False for it as well.
+        self.transd_step = bool(self.transd and self.want_fused and L.load().ktup_train_transd_step_supported(E.shape[1])
+                                and all(t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(1) == 1 and t.grad is not None
+                                        and t.grad.data_ptr() % 16 == 0 and t.grad.stride() == t.stride() for t in self.tabs))
         self.rws = None
         if self.transr and not self.transr_step:             # scratch of the relation-bucketed forward (K4)
             nbytes = L.load().ktup_score_transr_workspace_bytes(2 * B, R.shape[0])
@@ -672,7 +685,17 @@ class KGStepper(_StepperBase):
         d = E.shape[1]
         pos, neg, gpos, gneg = self.score[:B], self.score[B:], self.gscore[:B], self.gscore[B:]
         calls = []
-        self.fused_step = self._fused_ok(-1 if (self.transr or self.transd) else (1 if self.transh else 2), d)      # (-1: no fused kernel; TransR's and TransD's steps stay multi-launch)
+        # (-1: no kernel of ktup_train_step_supported; TransR's and TransD's one-launch steps are `transr_step` / `transd_step`.  TransD's
+        # has the one-workgroup form of option `deterministic`, so it is not refused under KTUP_DETERMINISTIC=1.)
+        self.fused_step = False if self.transd_step else \
+            self._fused_ok(-1 if (self.transr or self.transd) else (1 if self.transh else 2), d)
+        if self.transd_step:
+            Ep, Rp = self.tabs[2], self.tabs[3]
+            self._transd_fused = b('ktup_train_transd_step', _p(E), E.stride(0), _p(R), R.stride(0), _p(Ep), Ep.stride(0), _p(Rp),
+                                   Rp.stride(0), d, _p(self.h2), _p(self.t2), _p(self.r2), B, self.l1, self.margin, 1.0, 6, _p(self.loss),
+                                   _p(E.grad), _p(R.grad), _p(Ep.grad), _p(Rp.grad), self._gn_ptr(), st)
+            self._calls = []
+            return
         if self.fused_step:
             Rn_ = self.tabs[2] if self.transh else None
             self._kg_fused = b('ktup_train_kg_step', int(self.transh), _p(E), E.stride(0), _p(R), R.stride(0), _p(Rn_),
@@ -734,11 +757,18 @@ class KGStepper(_StepperBase):
             self._transr_fused()
             self._optimizer_launches(loss=(_p(self.loss), 4, 1.0, _p(self.out['kg']), self._acc_ptr('kg')))
             return self.out['kg']
+        if self.transd_step:             # one launch: both TransD scores, marginLoss, the two regularisers, the gradients of all four tables
+            self._transd_fused()
+            self._optimizer_launches(loss=(_p(self.loss), 4, 1.0, _p(self.out['kg']), self._acc_ptr('kg')), tracked=self._gn is not None)
+            return self.out['kg']
         self.loss.zero_()
         for launch in self._calls:
             launch()
         self._optimizer_launches()
         return self.loss[:4].sum()
+
+    def _feedable(self):
+        return self.fused_step or self.transd_step
 
     def kg_step(self, ph, pt, pr, nh, nt, nr):
         if self._never_capture:          # the bucketed TransR route: issued launch by launch, as BaselineJointStepper.kg_step does for CKE
