@@ -1,10 +1,12 @@
 """GPU-resident training steps of the three drivers: the arithmetic of their `train_loop` step bodies
 (knowledgable_recommendation.py:330-401 -> JointStepper; item_recommendation.py:160-195 -> RecStepper;
 knowledge_representation.py:176-211 -> KGStepper) through the C ABI and, in a single process, replayed from one HIP graph per
-step kind.  Where a fused kernel exists (ktup_train_step_supported: TUP / KTUP at d in {64, 100, 128}, TransH / TransE at any
-d % 4 == 0) a step is TWO launches: ktup_train_rec_step or ktup_train_kg_step (scores, loss, regularisers, every gradient) and
-ktup_optim_clip_step (norm, clip, optimizer, zero-fill of the gradients).  Otherwise (and with KTUP_FUSED_STEP=0) the round-1 sequence of about a dozen
-launches runs: same arithmetic, separate kernels.
+step kind.  Where a one-launch step kernel exists (ktup_train_step_supported: TUP / KTUP at d in {64, 100, 128}, TransH / TransE at
+any d % 4 == 0; ktup_train_transr_step; ktup_train_transd_step) a step is that launch -- scores, loss, regularisers, every gradient --
+and ktup_optim_clip_step (norm, clip, optimizer, zero-fill of the gradients): TWO launches, FIVE for TUP, whose three row
+regularisers are launches of their own between the two.  Otherwise (and with KTUP_FUSED_STEP=0) the round-1 sequence of about a
+dozen launches runs: same arithmetic, separate kernels.  The argument lists of the launches that more than one stepper binds are
+written once, in utils/step_plans.py; when a step is issued, captured or replayed is decided in one place, `_StepperBase._run`.
 
 The autograd route (`model(...)`, `bprLoss`, `.backward()`, `clip_and_step`) costs ~50 launches and ~0.5 ms of Python per
 B=512 step: every Function allocates and zero-fills table-shaped gradients which autograd then adds into `.grad`, and
@@ -22,20 +24,21 @@ rec step (knowledgable_recommendation.py:335-344):  bprLoss(pos, neg, target=-1)
 kg step  (:345-382):  kg_lambda * ( marginLoss(pos, neg, margin) + orthogonalLoss(rel, norm)[rel ids]
                                     + normLoss(ent)[h, t ids of pos and neg] + normLoss(rel)[rel ids] )
 """
+import os
+
 import torch
 import torch.distributed as dist
 
 from jTransUP.hip import lib as L
 from jTransUP.hip import ops
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
+from jTransUP.utils import step_plans as plans
+from jTransUP.utils.step_plans import _p
 
 
 class _StepperBase(object):
     """Shared machinery: flat gradient bucket (grads are views, 8 loss scalars at its end), data-parallel slice + all-reduce,
-    pre-bound launches, HIP-graph replay, the K20 clip + step."""
+    pre-bound launches, HIP-graph replay, the K20 clip + step.  A subclass gives `_setup`, `_bind` (the launch plans) and
+    `_rec_launches` / `_kg_launches` (a step's launches on bound plans and packed ids; they return the step's loss tensor)."""
 
     KINDS = ()        # step kinds of the subclass, e.g. ('rec', 'kg'), with the number of id tensors each takes
     N_IDS = {}
@@ -78,22 +81,20 @@ class _StepperBase(object):
         # position lives in device memory, KTUP_GUMBEL_PHILOX_DEV), so the launches of a step replay as ONE graph launch
         # (KTUP_TRAIN_GRAPHS=0 disables).  Inputs are copied into fixed buffers first.
         if use_graphs is None:
-            import os
             use_graphs = os.environ.get('KTUP_TRAIN_GRAPHS', '1') != '0'
         # Data-parallel replicas: the step is still ONE graph -- fused step kernel, the all-reduce of the flat bucket (RCCL
         # collectives are capturable), clip + optimizer launch -- when the backend is nccl; under the gloo test hook the
         # all-reduce is staged through the host and the launches are issued one by one (KTUP_DP_GRAPHS=0 forces that too)
-        import os as _os0
         # Several ranks: capturing the all-reduce inside the step's graph is exercised over RCCL at world 1 only (this repo's boxes
         # have one GPU), so it is opt-in there (KTUP_DP_GRAPHS=1) and the default issues the launches and the collective one by
         # one; every rank takes the same route (same environment, same step counts).
-        dp_ok = self.world == 1 or (dist.get_backend(group) == 'nccl' and _os0.environ.get('KTUP_DP_GRAPHS', '0') == '1')
+        dp_ok = self.world == 1 or (dist.get_backend(group) == 'nccl' and os.environ.get('KTUP_DP_GRAPHS', '0') == '1')
         if dist.is_initialized() and self.world == 1 and dist.get_backend(group) != 'nccl':
             from jTransUP import parallel as _par
             dp_ok = not _par._FORCE[0]              # forced collectives on gloo stage through the host: not capturable
         self.use_graphs = bool(use_graphs) and dp_ok
-        import os as _os
-        self.want_fused = _os.environ.get('KTUP_FUSED_STEP', '1') != '0'
+        self.never_captured = frozenset()           # step kinds whose launches are always issued one by one (a subclass says why)
+        self.want_fused = os.environ.get('KTUP_FUSED_STEP', '1') != '0'
         self.out = {k: torch.zeros((), **f32) for k in self.KINDS}                       # fused steps: where the step's loss is published
         # the gradient norm without a pass over the gradients (include/ktup_hip.h `gnorm`): the fused step kernels track the squared
         # norm of the buffers their atomics build, ktup_optim_clip_step reads it -- one process only (an all-reduce of the gradients
@@ -102,7 +103,7 @@ class _StepperBase(object):
         self._gn = None
         # (FM's and coFM's first parameter is their global bias, one element: their steps track no norm)
         if self.world == 1 and self.max_norm > 0 and self.tabs[0].dim() == 2 and self.tabs[0].shape[1] <= 128 \
-                and _os.environ.get('KTUP_TRACKED_NORM', '1') != '0':
+                and os.environ.get('KTUP_TRACKED_NORM', '1') != '0':
             self._gn = torch.zeros(64, dtype=torch.float64, device=dev)                 # KTUP_GNORM_WS_DOUBLES
         self._graphs = {}
         self._eager_steps = {k: 0 for k in self.KINDS}
@@ -111,6 +112,7 @@ class _StepperBase(object):
         self._feeds, self._sampler, self._feed_launch, self._feed_ok = {}, None, {}, {}
         self._acc_on = False
         self.acc = {k: torch.zeros((), **f32) for k in self.KINDS}                       # fed steps: running sum of the steps' losses
+        self.gstate = self.guni = None              # the hard preference gate: device stream position (_gumbel_stream), parity uniforms
         self._setup(FLAGS, f32, i64)
 
     # ------------------------------------------------------------------------------------------------ device-fed steps
@@ -161,172 +163,18 @@ class _StepperBase(object):
             v.zero_()
         return out
 
-    def fed_cycle(self, kinds):
-        """len(kinds) consecutive fed steps as ONE graph replay (hipGraphLaunch + the Python around it cost ~5 us per replay --
-        a tenth of a step).  Returns len(kinds), or 0 when the cycle cannot run right now: before every kind has its
-        single-step graph (warm-up, lazy optimizer state), after the optimizer was re-created, or when a feeder's epoch ends
-        inside the cycle (the host reshuffles between replays, never inside one)."""
-        fused = self.trainer.fused
-        if not (self.use_graphs and fused.graph_safe()):
-            return 0
-        count = {}
-        for kind in kinds:
-            count[kind] = count.get(kind, 0) + 1
-        for kind, c in count.items():
-            entry = self._graphs.get(kind + '+fed')
-            feed = self._feeds.get(kind)
-            if entry is None or entry[2] is not fused or feed.start + (c - 1) * self.B > feed.n - self.B:
-                return 0
-        for kind, c in count.items():
-            for _ in range(c):
-                self._feeds[kind].fed()
-                self._sampler.fed(self.B, kind)
-        gkey = 'cycle:' + ','.join(kinds)
-        entry = self._graphs.get(gkey)
-        if entry is not None and entry[2] is not fused:
-            entry = None
-        if entry is None:
-            graph = torch.cuda.CUDAGraph()
-            import os as _os
-            ahead = _os.environ.get('KTUP_FEED_AHEAD', '0') != '0'      # measured, round 5: 0.0456 against 0.0434 ms per step -- off
-            with L.capture(graph):
-                self._acc_on = True
-                try:
-                    if ahead:
-                        self._capture_cycle_feeds_ahead(kinds)
-                    else:
-                        for kind in kinds:
-                            self._plans()
-                            self._feed_launch[kind]()
-                            (self._rec_eager if kind == 'rec' else self._kg_eager)(*((None,) * self.N_IDS[kind]))
-                finally:
-                    self._acc_on = False
-            self._keys = None
-            fused._plan = None
-            entry = (graph, None, fused)
-            self._graphs[gkey] = entry
-            captured = True
-        else:
-            captured = False
-        entry[0].replay()
-        if not captured:
-            fused.bump_steps(len(kinds))
-            for kind, c in count.items():
-                self.fed_replays[kind] += c
-        self.trainer.step += len(kinds)
-        return len(kinds)
-
-    def _capture_cycle_feeds_ahead(self, kinds):
-        """The launches of a fed cycle with the FEEDS on a second branch of the graph: a feed depends on the sampler's state and the
-        cursor only, never on a step's result, so all of the cycle's feeds run back to back beside the chain
-        step kernel -> clip + optimizer -> step kernel -> ..., each into id buffers of its own (step k reads slot k), and step k waits
-        for feed k alone -- which has long finished when the chain gets there (ten feeds take ~90 us, the chain ~350).  The feeds
-        would leave the critical path but for the first one: ~8 of a step's ~43 us.  (Round 4 tried the fork / join PER STEP: the
-        cross-queue hand-over cost more than the feed it hid; here the graph forks once.)  Same feed kernels in the same order on
-        one queue, so the batches are the single-step route's (tests/test_fast_train.py runs under either setting).
-        MEASURED (round 5, tools/step_time.py): 0.0456 ms per step against 0.0434 with the feeds in the chain -- ten cross-queue
-        dependency edges cost more than the ten feeds they hide -- so this form is opt-in (KTUP_FEED_AHEAD=1), kept as the record
-        of the experiment."""
-        main = torch.cuda.current_stream(self.dev)
-        if getattr(self, '_feed_side', None) is None:
-            self._feed_side = torch.cuda.Stream(device=self.dev)
-        side = self._feed_side
-        i64 = dict(dtype=torch.int64, device=self.dev)
-        saved = {k: getattr(self, k, None) for k in ('_ids_rec', 'u2', 'i2', '_ids_kg', 'h2', 't2', 'r2', 'ht4')}
-        slots = []
-        try:
-            for kind in kinds:                                   # slot buffers with the layout of _id_buffers
-                self._id_buffers(kind, i64)
-                slots.append({k: getattr(self, k) for k in (('_ids_rec', 'u2', 'i2') if kind == 'rec' else ('_ids_kg', 'h2', 't2', 'r2', 'ht4'))})
-            self._cycle_slots = getattr(self, '_cycle_slots', []) + [slots]        # keep them alive as long as the graphs
-            side.wait_stream(main)
-            events = []
-            with torch.cuda.stream(side):
-                for kind, slot in zip(kinds, slots):
-                    for k, v in slot.items():
-                        setattr(self, k, v)
-                    self._make_feed(kind, side.cuda_stream)()
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-                    events.append(ev)
-            for kind, slot, ev in zip(kinds, slots, events):
-                for k, v in slot.items():
-                    setattr(self, k, v)
-                self._keys = None                                # bind the step's launches to this slot's buffers
-                self._plans()
-                main.wait_event(ev)
-                (self._rec_eager if kind == 'rec' else self._kg_eager)(*((None,) * self.N_IDS[kind]))
-            main.wait_stream(side)
-        finally:
-            for k, v in saved.items():
-                if v is not None:
-                    setattr(self, k, v)
-            self._keys = None
-
-    def fed_step(self, kind):
-        """One step of `kind` on the feeder's next batch: the step's graph is  feed launch -> step kernel -> clip + optimizer
-        launch, and the host does nothing but replay it.  The optimizer launch adds the step's loss to `acc[kind]` (take_sums).
-        (Drawing the NEXT batch on a side stream beside the optimizer launch was built and measured: the fork / join inside the
-        graph costs more than the 8 us it hides -- 56 vs 50 us per step.)"""
-        feed, sm, fused = self._feeds[kind], self._sampler, self.trainer.fused
-        eager = self._rec_eager if kind == 'rec' else self._kg_eager
-        nones = (None,) * self.N_IDS[kind]
-
-        def fed_eager():
-            self._plans()
-            self._feed_launch[kind]()
-            self._acc_on = True
-            try:
-                return eager(*nones)
-            finally:
-                self._acc_on = False
-
-        feed.fed()
-        sm.fed(self.B, kind)
-        if not (self.use_graphs and fused.graph_safe()):
-            out = fed_eager()
-            self.trainer.step += 1
-            return out
-        gkey = kind + '+fed'
-        entry = self._graphs.get(gkey)
-        if entry is not None and entry[2] is not fused:       # the trainer re-created its optimizer (LR decay): capture again
-            entry = None
-            self._eager_steps[kind] = 0
-        if entry is None and self._eager_steps[kind] < 2:
-            self._eager_steps[kind] += 1
-            out = fed_eager()
-            self.trainer.step += 1
-            return out
-        if entry is None:
-            graph = torch.cuda.CUDAGraph()
-            with L.capture(graph):
-                out = fed_eager()
-            self._keys = None                                 # plans were bound to the capture stream: rebind for eager use
-            fused._plan = None
-            entry = (graph, out, fused)
-            self._graphs[gkey] = entry
-            captured = True
-        else:
-            captured = False
-        entry[0].replay()
-        if not captured:
-            fused.bump_steps()
-            self.fed_replays[kind] += 1
-        self.trainer.step += 1
-        return entry[1]
-
     def _gumbel_stream(self, draws_per_step):
-        """(mode, pointer argument) of the preference gate, and the device-side stream position for the hard gate:
-        uint64[2] = {seed, offset}; `_gumbel_advance()` moves the offset past a step's draws (a captured launch)."""
+        """The device-side stream position of the hard preference gate: uint64[2] = {seed, offset}; `_gumbel_advance()` moves the
+        offset past a step's draws (a captured launch).  Without the gate `gstate` stays None."""
         if not getattr(self.m, 'use_st_gumbel', False):
-            self.gstate = None
             return
         seed = (int(self.m._gumbel.seed) * 6364136223846793005 + 1442695040888963407) % (1 << 62)   # own stream, apart from eval's
         self.gstate = torch.tensor([seed, 0], dtype=torch.int64, device=self.dev)
         self.gadv = torch.tensor([0, int(draws_per_step)], dtype=torch.int64, device=self.dev)
 
     def _gate_args(self):
-        if self.gstate is not None and getattr(self, 'guni', None) is not None:
+        """(mode, pointer argument) of the preference gate."""
+        if self.gstate is not None and self.guni is not None:
             return (ops.GUMBEL_INPUT, _p(self.guni))
         return (ops.GUMBEL_OFF, None) if self.gstate is None else (ops.GUMBEL_PHILOX_DEV, _p(self.gstate))
 
@@ -337,13 +185,13 @@ class _StepperBase(object):
         if self.gstate is None:
             raise L.KtupError('the model has no ST-Gumbel gate')
         if uniforms is None:
-            if getattr(self, 'guni', None) is not None:    # bound launches and captured graphs still point at the uniform buffer
+            if self.guni is not None:                  # bound launches and captured graphs still point at the uniform buffer
                 self._keys = None
                 self._graphs = {}
                 self._eager_steps = {k: 0 for k in self.KINDS}
             self.guni = None
         else:
-            if getattr(self, 'guni', None) is None:
+            if self.guni is None:
                 self.guni = torch.empty(2 * self.B, uniforms.shape[1], dtype=torch.float32, device=self.dev)
                 self._keys = None                      # re-bind the launches with the new gate arguments
                 self._graphs = {}
@@ -363,11 +211,12 @@ class _StepperBase(object):
         B = self.B
         if kind == 'rec':
             self._ids_rec = torch.zeros(4 * B, **i64)
-            self.u2, self.i2 = self._ids_rec[:2 * B], self._ids_rec[2 * B:]              # [u ; u], [pos ; neg]
+            self.u2, self.i2 = self.rec_ids = self._ids_rec[:2 * B], self._ids_rec[2 * B:]     # [u ; u], [pos ; neg]
         else:
             self._ids_kg = torch.zeros(10 * B, **i64)
             self.h2, self.t2, self.r2 = self._ids_kg[:2 * B], self._ids_kg[2 * B:4 * B], self._ids_kg[4 * B:6 * B]
             self.ht4 = self._ids_kg[6 * B:]                                              # ph, pt, nh, nt (normLoss rows)
+            self.kg_ids = (self.h2, self.t2, self.r2, self.ht4)
 
     def _pack(self, kind, args):
         if kind == 'rec':
@@ -377,12 +226,17 @@ class _StepperBase(object):
             ph, pt, pr, nh, nt, nr = (self._mine(x) for x in args)
             torch.cat((ph, nh, pt, nt, pr, nr, ph, pt, nh, nt), out=self._ids_kg)
 
+    def _g(self, t):
+        """Pointer of table t's gradient buffer (what the launch plans write into and `_plans` keys on)."""
+        return t.grad.data_ptr()
+
     def _plans(self):
+        """Every launch of a step has fixed arguments (persistent buffers): marshal them once (lib.bind).  Re-done when a table's
+        or a gradient's storage moves (load_state_dict keeps storages, so in practice never) or the stream changes (graph capture)."""
         st = torch.cuda.current_stream(self.dev).cuda_stream
-        if self._keys is None or st != self._stream or \
-                self._keys != tuple(t.data_ptr() for t in self.tabs) + tuple(t.grad.data_ptr() for t in self.tabs):
-            self._keys = tuple(t.data_ptr() for t in self.tabs) + tuple(t.grad.data_ptr() for t in self.tabs)
-            self._stream = st
+        keys = tuple(t.data_ptr() for t in self.tabs) + tuple(self._g(t) for t in self.tabs)
+        if self._keys != keys or st != self._stream:
+            self._keys, self._stream = keys, st
             self._bind(st)
             if self._feeds:
                 self._bind_feeds(st)
@@ -403,39 +257,111 @@ class _StepperBase(object):
             raise L.KtupError('KTUP_DETERMINISTIC=1 needs a fused step kernel; this shape (kind %d, d=%d, n_pref=%d) has none' % (kind, d, n_pref))
         return ok
 
-    def _step(self, kind, eager, args):
-        fused = self.trainer.fused
-        if not (self.use_graphs and fused.graph_safe()):
-            out = eager(*args)
-            self.trainer.step += 1
-            return out
-        entry = self._graphs.get(kind)
-        if entry is not None and entry[2] is not fused:       # the trainer re-created its optimizer (LR decay): capture again
+    # ------------------------------------------------------------------------------------------------ issue, capture, replay
+    def _launches(self, kind, ids, fed):
+        """One step's launches on the current stream: the feed launch (fed) or the id pack (host-fed; ids None: already packed),
+        then the kind's own launches.  Returns the step's loss tensor."""
+        self._plans()
+        if fed:
+            self._feed_launch[kind]()
+        elif ids is not None:
+            self._pack(kind, ids)                                # ids -> the persistent [pos ; neg] buffers
+        self._acc_on = fed
+        try:
+            return self._rec_launches() if kind == 'rec' else self._kg_launches()
+        finally:
+            self._acc_on = False
+
+    def _run(self, gkey, kinds, ids=None, fed=False, cycle=False):
+        """The steps `kinds` -- ONE step (`_step`, `fed_step`) or a cycle of device-fed steps (`fed_cycle`) -- issued launch by
+        launch, or captured into / replayed from the graph `_graphs[gkey]` = (graph, output tensor, the optimizer it was captured
+        with).  Host-fed steps bring `ids`; fed steps draw their batches on the device.  The rules, all of them:
+
+        - Eager route: when `use_graphs` is off, `fused.graph_safe()` is false or a kind is in `never_captured`.  A cycle returns 0.
+        - An entry whose third element is not the trainer's current `fused` (the trainer re-created its optimizer: LR decay) is
+          dropped.  For a single step this also resets the kind's warm-up counter; a cycle does not reset it.
+        - A cycle returns 0 -- before any host accounting -- whenever a kind's '+fed' entry is missing or stale (warm-up, lazy
+          optimizer state) or a feeder's epoch would end inside the cycle (the host reshuffles between replays, never inside one).
+        - Two eager warm-up steps per kind (allocations, lazy optimizer state) come before its first capture, counted in ONE
+          counter that `kind` and `kind + '+fed'` share.
+        - Host-fed steps pack their ids (`_pack`) before the capture or the replay, outside the graph; the captured body gets None.
+        - Fed steps call `feed.fed()` and `sampler.fed(B, kind)` before anything else, the eager route included.
+        - `_acc_on` is true only around a fed body (`_launches`).
+        - After a capture `_keys = None` and `fused._plan = None`: both were bound to the capture stream.
+        - `bump_steps(n)` and the `replays` / `fed_replays` counters advance on replays only: the capturing pass already ran the
+          host side of clip_and_step (its graph is launched once too).
+        - `trainer.step` advances by the number of steps in every case.
+        Returns the step's loss tensor (for a graph: the captured output, entry[1]), or the step count for a cycle."""
+        fused, kind, n = self.trainer.fused, kinds[0], len(kinds)
+        graphs = self.use_graphs and fused.graph_safe() and self.never_captured.isdisjoint(kinds)
+        if cycle:
+            if not graphs:
+                return 0
+            count = {}
+            for k in kinds:
+                count[k] = count.get(k, 0) + 1
+            for k, c in count.items():
+                entry, feed = self._graphs.get(k + '+fed'), self._feeds.get(k)
+                if entry is None or entry[2] is not fused or feed.start + (c - 1) * self.B > feed.n - self.B:
+                    return 0
+        if fed:
+            for k in kinds:
+                self._feeds[k].fed()
+                self._sampler.fed(self.B, k)
+        entry = self._graphs.get(gkey) if graphs else None
+        if entry is not None and entry[2] is not fused:
             entry = None
-            self._eager_steps[kind] = 0
-        if entry is None and self._eager_steps[kind] < 2:       # the first steps run eagerly (allocations, lazy optimizer state)
-            self._eager_steps[kind] += 1
-            out = eager(*args)
+            if not cycle:
+                self._eager_steps[kind] = 0
+        if not graphs or (entry is None and not cycle and self._eager_steps[kind] < 2):
+            if graphs:
+                self._eager_steps[kind] += 1
+            out = self._launches(kind, ids, fed)
             self.trainer.step += 1
             return out
-        self._pack(kind, args)                                   # ids -> the persistent [pos ; neg] buffers (outside the graph)
+        if not fed:
+            self._pack(kind, ids)
         if entry is None:
             graph = torch.cuda.CUDAGraph()
             with L.capture(graph):
-                out = eager(*([None] * len(args)))               # None: ids are already packed
-            self._keys = None                                    # plans were bound to the capture stream: rebind for eager use
+                for k in kinds:
+                    out = self._launches(k, None, fed)
+            self._keys = None
             fused._plan = None
-            entry = (graph, out, fused)
-            self._graphs[kind] = entry
-            captured = True                                      # the capture pass already ran the host side of clip_and_step
+            entry = self._graphs[gkey] = (graph, None if cycle else out, fused)
+            graph.replay()
         else:
-            captured = False
-        entry[0].replay()
-        if not captured:
-            fused.bump_steps()
-            self.replays[kind] += 1
-        self.trainer.step += 1
-        return entry[1]
+            entry[0].replay()
+            fused.bump_steps(n)
+            counter = self.fed_replays if fed else self.replays
+            for k in kinds:
+                counter[k] += 1
+        self.trainer.step += n
+        return n if cycle else entry[1]
+
+    def _step(self, kind, ids):
+        return self._run(kind, (kind,), ids)
+
+    def fed_step(self, kind):
+        """One step of `kind` on the feeder's next batch: the step's graph is  feed launch -> step kernel -> clip + optimizer
+        launch, and the host does nothing but replay it.  The optimizer launch adds the step's loss to `acc[kind]` (take_sums).
+        (Drawing the NEXT batch on a side stream beside the optimizer launch was built and measured: the fork / join inside the
+        graph costs more than the 8 us it hides -- 56 vs 50 us per step.)"""
+        return self._run(kind + '+fed', (kind,), fed=True)
+
+    def fed_cycle(self, kinds):
+        """len(kinds) consecutive fed steps as ONE graph replay (hipGraphLaunch + the Python around it cost ~5 us per replay --
+        a tenth of a step).  Returns len(kinds), or 0 when the cycle cannot run right now (`_run`)."""
+        return self._run('cycle:' + ','.join(kinds), kinds, fed=True, cycle=True)
+
+    # ------------------------------------------------------------------------------------------------ public steps
+    def rec_step(self, u, pi, ni):
+        """u, pi, ni: int64 device tensors of the GLOBAL batch.  Returns the step's loss (0-dim device tensor)."""
+        return self._step('rec', (u, pi, ni))
+
+    def kg_step(self, ph, pt, pr, nh, nt, nr):
+        return self._step('kg', (ph, pt, pr, nh, nt, nr))
+
 
 class JointStepper(_StepperBase):
     """KTUP (jtransup, own tables): knowledgable_recommendation.py:330-401."""
@@ -457,25 +383,16 @@ class JointStepper(_StepperBase):
 
     # ------------------------------------------------------------------------------------------------ launch plans
     def _bind(self, st):
-        """Every launch of a step has fixed arguments (persistent buffers): marshal them once (lib.bind).  Re-done when a
-        table's storage moves (load_state_dict keeps storages, so in practice never) or the stream changes (graph capture)."""
         U, I, E, P, Pn, R, Rn = self.tabs
-        B = self.B
+        B, b, g = self.B, L.bind, self._g
         n_pref, d = P.shape
-        n_rel = min(R.shape[0], Rn.shape[0])
         pos, neg, gpos, gneg = self.score[:B], self.score[B:], self.gscore[:B], self.gscore[B:]
         gate, gptr = self._gate_args()
-        b = L.bind
         self.fused_step = self._fused_ok(0, d, n_pref) and self._fused_ok(1, d)
         if self.fused_step:
-            inv = 1.0 / self.world
-            self._rec_fused = b('ktup_train_rec_step', _p(U), U.stride(0), _p(I), I.stride(0), _p(E), E.stride(0), _p(self.i2e), self.ent_pad,
-                                _p(P), _p(Pn), _p(R), _p(Rn), P.stride(0), n_pref, d, _p(self.u2), _p(self.i2), B, self.l1, gate, gptr, 0, 0,
-                                self.target, inv, 1, _p(self.loss), _p(U.grad), _p(I.grad), _p(E.grad), _p(P.grad), _p(Pn.grad),
-                                _p(R.grad), _p(Rn.grad), self._gn_ptr(), st)
-            self._kg_fused = b('ktup_train_kg_step', 1, _p(E), E.stride(0), _p(R), R.stride(0), _p(Rn), Rn.stride(0), d, _p(self.h2),
-                               _p(self.t2), _p(self.r2), B, self.l1, self.margin, self.kg_lambda, 7, _p(self.loss), _p(E.grad),
-                               _p(R.grad), _p(Rn.grad), self._gn_ptr(), st)
+            self._rec_fused = plans.rec_step(U, I, P, Pn, self.rec_ids, B, self.l1, (gate, gptr), self.target, 1.0 / self.world, self.loss,
+                                             g, self._gn_ptr(), st, E=E, i2e=self.i2e, ent_pad=self.ent_pad, R=R, Rn=Rn)
+            self._kg_fused = plans.kg_step(E, R, Rn, self.kg_ids, B, self.l1, self.margin, self.kg_lambda, self.loss, g, self._gn_ptr(), st)
         self._rec_head = [
             b('ktup_pref_prepare', _p(P), _p(Pn), _p(R), _p(Rn), P.stride(0), n_pref, d, _p(self.ws), st)]
         self._rec_soft = [
@@ -491,24 +408,11 @@ class JointStepper(_StepperBase):
         self._rec_tail = [
             b('ktup_reg_orth_fused', _p(P), P.stride(0), _p(Pn), Pn.stride(0), d, None, n_pref, _p(self.inv_world), _p(self.loss[1:]),
               _p(P.grad), _p(Pn.grad), st)]
-        self._kg = [
-            b('ktup_score_transh_fwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(Rn), Rn.stride(0), n_rel, d, _p(self.h2),
-              _p(self.t2), _p(self.r2), 2 * B, self.l1, _p(self.score), st),
-            b('ktup_loss_margin_fused', _p(pos), _p(neg), B, self.margin, _p(self.lam), _p(self.loss[0:]), _p(gpos), _p(gneg), st),
-            b('ktup_score_transh_bwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(Rn), Rn.stride(0), d, _p(self.h2), _p(self.t2),
-              _p(self.r2), 2 * B, self.l1, _p(self.gscore), _p(E.grad), _p(R.grad), _p(Rn.grad), st),
-            b('ktup_reg_orth_fused', _p(R), R.stride(0), _p(Rn), Rn.stride(0), d, _p(self.r2), 2 * B, _p(self.lam), _p(self.loss[1:]),
-              _p(R.grad), _p(Rn.grad), st),
-            b('ktup_reg_norm_fused', _p(E), E.stride(0), d, _p(self.ht4), 4 * B, _p(self.lam), _p(self.loss[2:]), _p(E.grad), st),
-            b('ktup_reg_norm_fused', _p(R), R.stride(0), d, _p(self.r2), 2 * B, _p(self.lam), _p(self.loss[3:]), _p(R.grad), st)]
+        self._kg = plans.kg_sequence('transh', (E, R, Rn), self.kg_ids, B, self.l1, self.margin, self.score, self.gscore, self.loss,
+                                     self.lam, g, st)
 
     # ------------------------------------------------------------------------------------------------ rec
-    def _rec_eager(self, u, pi, ni):
-        m, B = self.m, self.B
-        U, I, E, P, Pn, R, Rn = self.tabs
-        self._plans()
-        if u is not None:
-            self._pack('rec', (u, pi, ni))
+    def _rec_launches(self):
         if self.fused_step:              # one launch: table mixing, both scores, bprLoss, backward, gradient fan-out, orthogonalLoss
             self._rec_fused()
             self._gumbel_advance()
@@ -516,6 +420,7 @@ class JointStepper(_StepperBase):
                 self.loss[:2].mul_(self.inv_world)
             self._optimizer_launches(loss=(_p(self.loss), 2, 1.0, _p(self.out['rec']), self._acc_ptr('rec')), tracked=True)
             return self.out['rec']
+        U, I, E, P, Pn, R, Rn = self.tabs
         self._rec_head[0]()
         self.gAC.zero_(); self.loss.zero_()
         self._rec_soft[0](); self._rec_loss[0](); self._rec_soft_bwd[0]()
@@ -529,10 +434,7 @@ class JointStepper(_StepperBase):
         return self.loss[0] + self.loss[1]
 
     # ------------------------------------------------------------------------------------------------ kg
-    def _kg_eager(self, ph, pt, pr, nh, nt, nr):
-        self._plans()
-        if ph is not None:
-            self._pack('kg', (ph, pt, pr, nh, nt, nr))
+    def _kg_launches(self):
         if self.fused_step:              # one launch: both TransH scores, marginLoss, the three regularisers, every gradient
             self._kg_fused()
             self._optimizer_launches(loss=(_p(self.loss), 4, self.kg_lambda, _p(self.out['kg']), self._acc_ptr('kg')), tracked=True)
@@ -542,14 +444,6 @@ class JointStepper(_StepperBase):
             launch()
         self._optimizer_launches()
         return self.kg_lambda * self.loss[:4].sum()
-
-    # ------------------------------------------------------------------------------------------------ public steps
-    def rec_step(self, u, pi, ni):
-        """u, pi, ni: int64 device tensors of the GLOBAL batch.  Returns the step's loss (0-dim device tensor)."""
-        return self._step('rec', self._rec_eager, (u, pi, ni))
-
-    def kg_step(self, ph, pt, pr, nh, nt, nr):
-        return self._step('kg', self._kg_eager, (ph, pt, pr, nh, nt, nr))
 
 
 class RecStepper(_StepperBase):
@@ -590,11 +484,9 @@ class RecStepper(_StepperBase):
         n_pref = P.shape[0]
         gate, gptr = self._gate_args()
         self.fused_step = self._fused_ok(0, d, n_pref)
-        if self.fused_step:
-            self._rec_fused = b('ktup_train_rec_step', _p(U), U.stride(0), _p(I), I.stride(0), None, 0, None, -1, _p(P), _p(Pn), None, None,
-                                P.stride(0), n_pref, d, _p(self.u2), _p(self.i2), B, self.l1, gate, gptr, 0, 0, self.target, 1.0 / self.world,
-                                1, _p(self.loss), _p(U.grad), _p(I.grad), None, _p(P.grad), _p(Pn.grad), None, None, None, st)   # (no tracked
-                                # norm: the row regularisers below add to the gradients after this launch)
+        if self.fused_step:              # (no tracked norm: the row regularisers below add to the gradients after this launch)
+            self._rec_fused = plans.rec_step(U, I, P, Pn, self.rec_ids, B, self.l1, (gate, gptr), self.target, 1.0 / self.world, self.loss,
+                                             self._g, None, st)
         self._prep = b('ktup_pref_prepare', _p(P), _p(Pn), None, None, P.stride(0), n_pref, d, _p(self.ws), st)
         self._fwd = b('ktup_score_tup_fwd', _p(U), U.stride(0), _p(I), I.stride(0), _p(self.ws), n_pref, d, _p(self.u2), _p(self.i2),
                       2 * B, self.l1, gate, gptr, 0, 0, _p(self.score), st)
@@ -607,11 +499,7 @@ class RecStepper(_StepperBase):
             b('ktup_reg_norm_fused', _p(I), I.stride(0), d, _p(self.i2), 2 * B, _p(self.one), _p(self.loss[3:]), _p(I.grad), st),  # pos and neg items
             b('ktup_reg_norm_fused', _p(P), P.stride(0), d, None, n_pref, _p(self.inv_world), _p(self.loss[4:]), _p(P.grad), st)]
 
-    def _rec_eager(self, u, pi, ni):
-        m, B = self.m, self.B
-        self._plans()
-        if u is not None:
-            self._pack('rec', (u, pi, ni))
+    def _rec_launches(self):
         self.loss.zero_()
         if not self.tup:
             self._fwd(); self._loss[0](); self._bwd()
@@ -641,9 +529,6 @@ class RecStepper(_StepperBase):
         self._optimizer_launches()
         return self.loss[:5].sum()
 
-    def rec_step(self, u, pi, ni):
-        return self._step('rec', self._rec_eager, (u, pi, ni))
-
 
 class KGStepper(_StepperBase):
     """KG-only driver (knowledge_representation.py:176-211) for TransE / TransH / TransR / TransD: marginLoss + normLoss(entity rows
@@ -657,6 +542,7 @@ class KGStepper(_StepperBase):
         self.transh = hasattr(model, 'norm_embeddings')
         self.transr = hasattr(model, 'proj_embeddings')
         self.transd = hasattr(model, 'ent_proj_embeddings')
+        self.model_kind = 'transh' if self.transh else 'transr' if self.transr else 'transd' if self.transd else 'transe'
         E, R = model.ent_embeddings.weight, model.rel_embeddings.weight
         self.tabs = (E, R, model.norm_embeddings.weight) if self.transh else (E, R, model.proj_embeddings.weight) if self.transr else (E, R)
         if self.transd:
@@ -666,8 +552,10 @@ class KGStepper(_StepperBase):
         self.transr_step = bool(self.transr and self.want_fused and L.load().ktup_train_transr_step_supported(E.shape[1])
                                 and 1 <= B <= 4096 and 1 <= min(R.shape[0], self.tabs[2].shape[0]) <= 4096)
         # The bucketed TransR kernels (d = 64, 100, 128) clear their counters with a memset into a pooled workspace; a captured
-        # memset node of that kind writes garbage from its second replay on, so that route is never captured.
-        self._never_capture = self.transr and not self.transr_step and E.shape[1] in (64, 100, 128)
+        # memset node of that kind writes garbage from its second replay on, so that route is never captured:
+        # it is issued launch by launch, as BaselineJointStepper's kg step is for CKE.
+        if self.transr and not self.transr_step and E.shape[1] in (64, 100, 128):
+            self.never_captured = frozenset(['kg'])
         # TransD: the whole step as ONE launch too (ktup_train_transd_step; KTUP_FUSED_STEP=0 keeps the multi-launch route).  It reads
         # the [pos ; neg] id arrays alone, so the device-fed steps take it (`_feedable`); `fused_step` stays False for it as well.
         self.transd_step = bool(self.transd and self.want_fused and L.load().ktup_train_transd_step_supported(E.shape[1])
@@ -680,75 +568,26 @@ class KGStepper(_StepperBase):
         self._id_buffers('kg', i64)
 
     def _bind(self, st):
-        B, b = self.B, L.bind
         E, R = self.tabs[0], self.tabs[1]
         d = E.shape[1]
-        pos, neg, gpos, gneg = self.score[:B], self.score[B:], self.gscore[:B], self.gscore[B:]
-        calls = []
+        step = (self.kg_ids, self.B, self.l1, self.margin, 1.0, self.loss, self._g)       # what the one-launch builders share
         # (-1: no kernel of ktup_train_step_supported; TransR's and TransD's one-launch steps are `transr_step` / `transd_step`.  TransD's
         # has the one-workgroup form of option `deterministic`, so it is not refused under KTUP_DETERMINISTIC=1.)
         self.fused_step = False if self.transd_step else \
             self._fused_ok(-1 if (self.transr or self.transd) else (1 if self.transh else 2), d)
+        self._calls = []
         if self.transd_step:
-            Ep, Rp = self.tabs[2], self.tabs[3]
-            self._transd_fused = b('ktup_train_transd_step', _p(E), E.stride(0), _p(R), R.stride(0), _p(Ep), Ep.stride(0), _p(Rp),
-                                   Rp.stride(0), d, _p(self.h2), _p(self.t2), _p(self.r2), B, self.l1, self.margin, 1.0, 6, _p(self.loss),
-                                   _p(E.grad), _p(R.grad), _p(Ep.grad), _p(Rp.grad), self._gn_ptr(), st)
-            self._calls = []
+            self._transd_fused = plans.transd_step(E, R, self.tabs[2], self.tabs[3], *step, self._gn_ptr(), st)
             return
         if self.fused_step:
-            Rn_ = self.tabs[2] if self.transh else None
-            self._kg_fused = b('ktup_train_kg_step', int(self.transh), _p(E), E.stride(0), _p(R), R.stride(0), _p(Rn_),
-                               Rn_.stride(0) if self.transh else 0, d, _p(self.h2), _p(self.t2), _p(self.r2), B, self.l1, self.margin, 1.0,
-                               7 if self.transh else 6, _p(self.loss), _p(E.grad), _p(R.grad), _p(Rn_.grad) if self.transh else None,
-                               self._gn_ptr(), st)
+            self._kg_fused = plans.kg_step(E, R, self.tabs[2] if self.transh else None, *step, self._gn_ptr(), st)
         if self.transr_step:
-            M = self.tabs[2]
-            self._transr_fused = b('ktup_train_transr_step', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0),
-                                   min(R.shape[0], M.shape[0]), d, _p(self.h2), _p(self.t2), _p(self.r2), B, self.l1, self.margin, 1.0, 6, 0,
-                                   _p(self.loss), _p(E.grad), _p(R.grad), _p(M.grad), st)
-            self._calls = []
+            self._transr_fused = plans.transr_step(E, R, self.tabs[2], *step, st)
             return
-        if self.transh:
-            Rn = self.tabs[2]
-            n_rel = min(R.shape[0], Rn.shape[0])
-            calls.append(b('ktup_score_transh_fwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(Rn), Rn.stride(0), n_rel, d, _p(self.h2),
-                           _p(self.t2), _p(self.r2), 2 * B, self.l1, _p(self.score), st))
-        elif self.transr:
-            M = self.tabs[2]
-            calls.append(b('ktup_score_transr_fwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0), min(R.shape[0], M.shape[0]),
-                           d, _p(self.h2), _p(self.t2), _p(self.r2), 2 * B, self.l1, _p(self.score), _p(self.rws), st))
-        elif self.transd:
-            Ep, Rp = self.tabs[2], self.tabs[3]
-            calls.append(b('ktup_score_transd_fwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(Ep), Ep.stride(0), _p(Rp), Rp.stride(0), d,
-                           _p(self.h2), _p(self.t2), _p(self.r2), 2 * B, self.l1, _p(self.score), st))
-        else:
-            calls.append(b('ktup_score_transe_fwd', _p(E), E.stride(0), _p(R), R.stride(0), R.shape[0], d, _p(self.h2), _p(self.t2), _p(self.r2),
-                           2 * B, self.l1, _p(self.score), st))
-        calls.append(b('ktup_loss_margin_fused', _p(pos), _p(neg), B, self.margin, _p(self.one), _p(self.loss[0:]), _p(gpos), _p(gneg), st))
-        if self.transh:
-            calls += [b('ktup_score_transh_bwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(Rn), Rn.stride(0), d, _p(self.h2), _p(self.t2),
-                        _p(self.r2), 2 * B, self.l1, _p(self.gscore), _p(E.grad), _p(R.grad), _p(Rn.grad), st),
-                      b('ktup_reg_orth_fused', _p(R), R.stride(0), _p(Rn), Rn.stride(0), d, _p(self.r2), 2 * B, _p(self.one),
-                        _p(self.loss[1:]), _p(R.grad), _p(Rn.grad), st)]
-        elif self.transr:
-            calls.append(b('ktup_score_transr_bwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0), d, _p(self.h2), _p(self.t2),
-                           _p(self.r2), 2 * B, self.l1, _p(self.gscore), _p(E.grad), _p(R.grad), _p(M.grad), st))
-        elif self.transd:
-            calls.append(b('ktup_score_transd_bwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(Ep), Ep.stride(0), _p(Rp), Rp.stride(0), d,
-                           _p(self.h2), _p(self.t2), _p(self.r2), 2 * B, self.l1, _p(self.gscore), _p(E.grad), _p(R.grad), _p(Ep.grad),
-                           _p(Rp.grad), st))
-        else:
-            calls.append(b('ktup_score_transe_bwd', _p(E), E.stride(0), _p(R), R.stride(0), d, _p(self.h2), _p(self.t2), _p(self.r2),
-                           2 * B, self.l1, _p(self.gscore), _p(E.grad), _p(R.grad), st))
-        calls += [b('ktup_reg_norm_fused', _p(E), E.stride(0), d, _p(self.ht4), 4 * B, _p(self.one), _p(self.loss[2:]), _p(E.grad), st),
-                  b('ktup_reg_norm_fused', _p(R), R.stride(0), d, _p(self.r2), 2 * B, _p(self.one), _p(self.loss[3:]), _p(R.grad), st)]
-        self._calls = calls
+        self._calls = plans.kg_sequence(self.model_kind, self.tabs, self.kg_ids, self.B, self.l1, self.margin, self.score, self.gscore,
+                                        self.loss, self.one, self._g, st, rws=self.rws)
 
-    def _kg_eager(self, ph, pt, pr, nh, nt, nr):
-        self._plans()
-        if ph is not None:
-            self._pack('kg', (ph, pt, pr, nh, nt, nr))
+    def _kg_launches(self):
         if self.fused_step:
             self._kg_fused()
             self._optimizer_launches(loss=(_p(self.loss), 4, 1.0, _p(self.out['kg']), self._acc_ptr('kg')), tracked=True)
@@ -769,13 +608,6 @@ class KGStepper(_StepperBase):
 
     def _feedable(self):
         return self.fused_step or self.transd_step
-
-    def kg_step(self, ph, pt, pr, nh, nt, nr):
-        if self._never_capture:          # the bucketed TransR route: issued launch by launch, as BaselineJointStepper.kg_step does for CKE
-            out = self._kg_eager(ph, pt, pr, nh, nt, nr)
-            self.trainer.step += 1
-            return out
-        return self._step('kg', self._kg_eager, (ph, pt, pr, nh, nt, nr))
 
 
 class DeviceFeeder(object):

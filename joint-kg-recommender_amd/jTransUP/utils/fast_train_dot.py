@@ -16,6 +16,7 @@ kg step:   kg_lambda * (marginLoss(pos, neg, margin) + normLoss(ent rows) + norm
 import torch
 
 from jTransUP.hip import lib as L
+from jTransUP.utils import step_plans as plans
 from jTransUP.utils.fast_train import _StepperBase, _p
 
 
@@ -45,28 +46,19 @@ class DotRecStepper(_StepperBase):
         if not dot_step_supported(self.tabs[0].shape[1]):
             raise L.KtupError('ktup_train_dot_step does not take embedding_size %d (or KTUP_DETERMINISTIC=1 is set)' % self.tabs[0].shape[1])
         self._id_buffers('rec', i64)
-        self.gstate = None
         self.fused_step = True
 
     def _bind(self, st):
         U, I = self.tabs[:2]
         bu, bi, gb = self.tabs[2:] if len(self.tabs) > 2 else (None, None, None)
         self.fused_step = True
-        self._rec_fused = L.bind('ktup_train_dot_step', _p(U), U.stride(0), _p(I), I.stride(0), None, 0, None, -1, _p(gb), _p(bu), _p(bi),
-                                 U.shape[1], _p(self.u2), _p(self.i2), self.B, self.target, 1.0 / self.world, _p(self.loss), _p(U.grad),
-                                 _p(I.grad), None, None if bi is None else _p(bi.grad), st)
+        self._rec_fused = plans.dot_step(U, I, self.rec_ids, self.B, self.target, 1.0 / self.world, self.loss, self._g, st,
+                                         bias=(gb, bu, bi))
 
-    def _rec_eager(self, u, pi, ni):
-        self._plans()
-        if u is not None:
-            self._pack('rec', (u, pi, ni))
+    def _rec_launches(self):
         self._rec_fused()
         self._optimizer_launches(loss=(_p(self.loss), 1, 1.0, _p(self.out['rec']), self._acc_ptr('rec')))
         return self.out['rec']
-
-    def rec_step(self, u, pi, ni):
-        """u, pi, ni: int64 device tensors of the GLOBAL batch.  Returns the step's loss (0-dim device tensor)."""
-        return self._step('rec', self._rec_eager, (u, pi, ni))
 
 
 class BaselineJointStepper(_StepperBase):
@@ -94,7 +86,6 @@ class BaselineJointStepper(_StepperBase):
         if not (cfkg_step_supported(d) if self.cfkg else dot_step_supported(d)):
             raise L.KtupError('%s does not take embedding_size %d (or KTUP_DETERMINISTIC=1 is set)'
                               % ('ktup_train_cfkg_rec_step' if self.cfkg else 'ktup_train_dot_step', d))
-        self.gstate = None
         self.lam = torch.full((), self.kg_lambda, **f32)               # upstream gradient of the multi-launch kg terms
         self._id_buffers('rec', i64); self._id_buffers('kg', i64)
         if self.cke:
@@ -110,6 +101,12 @@ class BaselineJointStepper(_StepperBase):
                 self.rws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=self.dev)
             self.align = False
             self.fused_step = False                                     # host-fed only
+            # The kg step is never captured: the relation-bucketed TransR kernels (d = 64, 100, 128) clear their counters in the
+            # workspace with hipMemsetAsync, and a captured memset node whose destination lies inside a pooled allocation writes garbage
+            # from its second replay on -- the bucket kernels then index past the workspace.  The rec step replays.
+            # (With `transr_step` the kg step is ktup_train_transr_step, which has no memset and replays safely; it is still
+            # issued eagerly here because the suite pins this stepper's graphs to {'rec'}.)
+            self.never_captured = frozenset(['kg'])
         elif self.cfkg:
             if I is not E:
                 raise L.KtupError('CFKG scores items on the entity table (-share_embeddings is forced)')
@@ -142,6 +139,7 @@ class BaselineJointStepper(_StepperBase):
 
     # ------------------------------------------------------------------------------------------------ late tables
     def _g(self, t):
+        """A sleeping table's `.grad` is None: the launch plans write into, and `_plans` keys on, its view of the flat bucket."""
         return self._views[id(t)].data_ptr()
 
     def _wake(self, kind):
@@ -157,13 +155,6 @@ class BaselineJointStepper(_StepperBase):
         self._keys = None
         self.trainer.fused._plan = None
 
-    def _plans(self):
-        st = torch.cuda.current_stream(self.dev).cuda_stream
-        keys = tuple(t.data_ptr() for t in self.tabs) + tuple(self._g(t) for t in self.tabs)
-        if self._keys != keys or st != self._stream:
-            self._keys, self._stream = keys, st
-            self._bind(st)
-
     def attach_feeds(self, sampler, **feeds):
         raise L.KtupError('the joint baselines take host-fed batches only')
 
@@ -174,28 +165,17 @@ class BaselineJointStepper(_StepperBase):
     def _bind(self, st):
         m, B, b, g = self.m, self.B, L.bind, self._g
         inv = 1.0 / self.world
-        pos, neg, gpos, gneg = self.score[:B], self.score[B:], self.gscore[:B], self.gscore[B:]
+        rec = (self.rec_ids, B, self.target, inv, self.loss, g, st)
+        kg = (self.kg_ids, B, self.l1, self.margin)
+        seq = (self.score, self.gscore, self.loss, self.lam, g, st)    # the multi-launch kg steps, with kg_lambda as the upstream scalar
         if self.cke:
             U, I, E, R, M = self.tabs
-            d = U.shape[1]
-            self._rec_fused = b('ktup_train_dot_step', _p(U), U.stride(0), _p(I), I.stride(0), _p(E), E.stride(0), _p(m._item2ent),
-                                m.ent_total - 1, None, None, None, d, _p(self.u2), _p(self.i2), B, self.target, inv, _p(self.loss),
-                                g(U), g(I), g(E), None, st)
+            self._rec_fused = plans.dot_step(U, I, *rec, E=E, i2e=m._item2ent, ent_pad=m.ent_total - 1)
+            self._kg = []
             if self.transr_step:
-                self._kg_transr = b('ktup_train_transr_step', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0),
-                                    min(R.shape[0], M.shape[0]), d, _p(self.h2), _p(self.t2), _p(self.r2), B, self.l1, self.margin,
-                                    self.kg_lambda, 6, 0, _p(self.loss), g(E), g(R), g(M), st)
-                self._kg = []
-                return
-            # the TransR sequence of KGStepper._bind, with kg_lambda as the upstream scalar
-            self._kg = [
-                b('ktup_score_transr_fwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0), min(R.shape[0], M.shape[0]), d,
-                  _p(self.h2), _p(self.t2), _p(self.r2), 2 * B, self.l1, _p(self.score), _p(self.rws), st),
-                b('ktup_loss_margin_fused', _p(pos), _p(neg), B, self.margin, _p(self.lam), _p(self.loss[0:]), _p(gpos), _p(gneg), st),
-                b('ktup_score_transr_bwd', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0), d, _p(self.h2), _p(self.t2),
-                  _p(self.r2), 2 * B, self.l1, _p(self.gscore), g(E), g(R), g(M), st),
-                b('ktup_reg_norm_fused', _p(E), E.stride(0), d, _p(self.ht4), 4 * B, _p(self.lam), _p(self.loss[2:]), g(E), st),
-                b('ktup_reg_norm_fused', _p(R), R.stride(0), d, _p(self.r2), 2 * B, _p(self.lam), _p(self.loss[3:]), g(R), st)]
+                self._kg_transr = plans.transr_step(E, R, M, *kg, self.kg_lambda, self.loss, g, st)
+            else:
+                self._kg = plans.kg_sequence('transr', (E, R, M), *kg, *seq, rws=self.rws)
             return
         if self.cfkg:
             U, E, R = self.tabs
@@ -206,20 +186,11 @@ class BaselineJointStepper(_StepperBase):
             U, bu, bi, gb, R, E = self.tabs[:6]
             I = self.tabs[6] if self.align else E
             d = U.shape[1]
-            self._rec_fused = b('ktup_train_dot_step', _p(U), U.stride(0), _p(I), I.stride(0), None, 0, None, -1, _p(gb), _p(bu), _p(bi), d,
-                                _p(self.u2), _p(self.i2), B, self.target, inv, _p(self.loss), g(U), g(I), None, g(bi), st)
+            self._rec_fused = plans.dot_step(U, I, *rec, bias=(gb, bu, bi))
         if self.kg_fused:
-            self._kg_fused = b('ktup_train_kg_step', 0, _p(E), E.stride(0), _p(R), R.stride(0), None, 0, d, _p(self.h2), _p(self.t2),
-                               _p(self.r2), B, self.l1, self.margin, self.kg_lambda, 6, _p(self.loss), g(E), g(R), None, None, st)
-        # (a width ktup_train_kg_step does not take, d % 4 != 0: the TransE sequence of KGStepper._bind)
-        self._kg = [
-            b('ktup_score_transe_fwd', _p(E), E.stride(0), _p(R), R.stride(0), R.shape[0], d, _p(self.h2), _p(self.t2), _p(self.r2), 2 * B,
-              self.l1, _p(self.score), st),
-            b('ktup_loss_margin_fused', _p(pos), _p(neg), B, self.margin, _p(self.lam), _p(self.loss[0:]), _p(gpos), _p(gneg), st),
-            b('ktup_score_transe_bwd', _p(E), E.stride(0), _p(R), R.stride(0), d, _p(self.h2), _p(self.t2), _p(self.r2), 2 * B, self.l1,
-              _p(self.gscore), g(E), g(R), st),
-            b('ktup_reg_norm_fused', _p(E), E.stride(0), d, _p(self.ht4), 4 * B, _p(self.lam), _p(self.loss[2:]), g(E), st),
-            b('ktup_reg_norm_fused', _p(R), R.stride(0), d, _p(self.r2), 2 * B, _p(self.lam), _p(self.loss[3:]), g(R), st)]
+            self._kg_fused = plans.kg_step(E, R, None, *kg, self.kg_lambda, self.loss, g, None, st)
+        # (for a width ktup_train_kg_step does not take, d % 4 != 0)
+        self._kg = plans.kg_sequence('transe', (E, R), *kg, *seq)
         if self.align:
             cap = self.al_cap
             # every rank applies the whole term (the lists come from the global batch), scaled 1 / world like the other replicated terms
@@ -254,25 +225,19 @@ class BaselineJointStepper(_StepperBase):
         return self.total[kind]
 
     # ------------------------------------------------------------------------------------------------ steps
-    def _rec_eager(self, u, pi, ni):
-        self._plans()
-        if u is not None:
-            self._pack('rec', (u, pi, ni))
+    def _rec_launches(self):
         self._rec_fused()
         return self._finish('rec', 1, 1.0)
 
-    def _kg_eager(self, ph, pt, pr, nh, nt, nr):
-        self._plans()
-        if ph is not None:
-            self._pack('kg', (ph, pt, pr, nh, nt, nr))
-        if not self.cke and self.kg_fused:
-            self._kg_fused()
-            return self._finish('kg', 4, self.kg_lambda)
-        if self.cke and self.transr_step:                               # one launch; gradients x kg_lambda, slots unscaled
+    def _kg_launches(self):
+        """One launch where there is one, else the multi-launch sequence: gradients x kg_lambda either way, slots unscaled."""
+        if self.cke and self.transr_step:
             self._kg_transr()
-            return self._finish('kg', 4, self.kg_lambda)
-        for launch in self._kg:                                         # gradients x kg_lambda (device scalar), slots unscaled
-            launch()
+        elif not self.cke and self.kg_fused:
+            self._kg_fused()
+        else:
+            for launch in self._kg:
+                launch()
         return self._finish('kg', 4, self.kg_lambda)
 
     def rec_step(self, u, pi, ni, align=None):
@@ -280,21 +245,12 @@ class BaselineJointStepper(_StepperBase):
         align = (entity ids, item ids), coFM with its own item table only.  Returns the step's loss (0-dim device tensor)."""
         self._wake('rec')
         self._take_alignment(align)
-        return self._step('rec', self._rec_eager, (u, pi, ni))
+        return self._step('rec', (u, pi, ni))
 
     def kg_step(self, ph, pt, pr, nh, nt, nr, align=None):
         self._wake('kg')
         self._take_alignment(align)
-        if self.cke:
-            # Never captured: the relation-bucketed TransR kernels (d = 64, 100, 128) clear their counters in the workspace with
-            # hipMemsetAsync, and a captured memset node whose destination lies inside a pooled allocation writes garbage from its
-            # second replay on (DESIGN.md section 8) -- the bucket kernels then index past the workspace.  The rec step replays.
-            # (With `transr_step` the kg step is ktup_train_transr_step, which has no memset and replays safely; it is still
-            # issued eagerly here because the suite pins this stepper's graphs to {'rec'}.)
-            out = self._kg_eager(ph, pt, pr, nh, nt, nr)
-            self.trainer.step += 1
-            return out
-        return self._step('kg', self._kg_eager, (ph, pt, pr, nh, nt, nr))
+        return self._step('kg', (ph, pt, pr, nh, nt, nr))
 
     def _take_alignment(self, align):
         if self.align:
