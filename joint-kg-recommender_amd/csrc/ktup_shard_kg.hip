@@ -10,7 +10,12 @@
 // group keeps the gradient of its current relation in registers across its consecutive triples, adds it to the workgroup's LDS
 // row when the relation is the workgroup's first one (the common case: 16 consecutive sorted triples share a relation) and the
 // workgroup flushes that row once -- ~512 x 2 x d atomics per step instead of 4 M.
-#include "ktup_rows.h"
+//
+// The arithmetic of a triple and its twin is kg_pair_math (ktup_kg_pair.h), the one copy kg_step_kernel (ktup_train_step.hip) runs too;
+// kg_step_rows_kernel keeps its prefetch, its stores, the relation walk and its own tail: the loss slots go out after the home
+// rows' flush and the sum of squares goes to caller slots as a double atomic, not to the gnorm workspace, through the same red[4][4]
+// (step_tail would bring a second LDS array for the loss half alone).
+#include "ktup_kg_pair.h"
 
 using namespace ktup;
 
@@ -100,7 +105,6 @@ __global__ __launch_bounds__(256) void kg_step_rows_kernel(KgRowsArgs a) {
   __syncthreads();
   float part[4] = {0.f, 0.f, 0.f, 0.f};
   float ssq = 0.f;
-  const float g1 = a.gscale;
   const int64_t p0 = p_wg + (int64_t)grp * a.chunk, p1 = min(a.B, p0 + (int64_t)a.chunk);
   float4 accR = f4zero(), accN = f4zero();
   int64_t cur = -1;
@@ -144,68 +148,8 @@ __global__ __launch_bounds__(256) void kg_step_rows_kernel(KgRowsArgs a) {
       rr[x] = on ? reinterpret_cast<const float4*>(a.R + t.rid[x] * a.ldr)[lane] : f4zero();
       ww[x] = (TRANSH && on) ? reinterpret_cast<const float4*>(a.Nm + t.rid[x] * a.ldn)[lane] : f4zero();
     }
-    // ---- forward of both triples (jTransUP.py:144-157 = transH.py:58-71; TransE: transE.py:51-63)
-    float dh[2] = {0.f, 0.f}, dt[2] = {0.f, 0.f}, sc[2];
-    float4 z[2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-      const float4 hh = t.e[2 * x], tt = t.e[2 * x + 1];
-      if (TRANSH) {
-        dh[x] = group_sum<GL>(dot4(hh, ww[x]));
-        dt[x] = group_sum<GL>(dot4(tt, ww[x]));
-        const float4 ph = fma4(-dh[x], ww[x], hh), pt = fma4(-dt[x], ww[x], tt);
-        z[x] = (ph + rr[x]) - pt;
-      } else {
-        z[x] = (hh + rr[x]) - tt;
-      }
-      sc[x] = group_sum<GL>(dist4(z[x], a.l1));
-    }
-    // ---- marginLoss (utils/loss.py:8-16): sum_k max(pos - neg + margin, 0)
-    const float diff = sc[0] - sc[1];
-    const bool act = diff + a.margin > 0.f;
-    if (lane == 0) part[0] += fmaxf(diff + a.margin, 0.f);
-    const float gs[2] = {act ? g1 : 0.f, act ? -g1 : 0.f};
-    float4 ge[4], gr[2], gw[2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-      const float4 gz = gs[x] * ddist4(z[x], a.l1);
-      if (TRANSH) {
-        const float aw = group_sum<GL>(dot4(gz, ww[x]));
-        const float sq = dh[x] - dt[x];
-        const float4 q = t.e[2 * x] - t.e[2 * x + 1];
-        ge[2 * x] = fma4(-aw, ww[x], gz);
-        ge[2 * x + 1] = -1.f * ge[2 * x];
-        gw[x] = fma4(-aw, q, (-sq) * gz);
-      } else {
-        ge[2 * x] = gz;
-        ge[2 * x + 1] = -1.f * gz;
-        gw[x] = f4zero();
-      }
-      gr[x] = gz;
-    }
-    if (a.regs & 2) {                 // normLoss(ent rows): sum max(|x|^2 - 1, 0)  (utils/loss.py:21-23)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const float s = group_sum<GL>(dot4(t.e[x], t.e[x]));
-        if (s - 1.f > 0.f) ge[x] = fma4(2.f * g1, t.e[x], ge[x]);
-        if (lane == 0) part[2] += fmaxf(s - 1.f, 0.f);
-      }
-    }
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-      if (TRANSH && (a.regs & 1)) {   // orthogonalLoss(rel rows, norm rows): sum (w.r)^2 / |r|^2  (utils/loss.py:18-19)
-        const float dot = group_sum<GL>(dot4(rr[x], ww[x])), nr = group_sum<GL>(dot4(rr[x], rr[x]));
-        const float c1 = g1 * 2.f * dot / nr, c2 = g1 * 2.f * dot * dot / (nr * nr);
-        gr[x] = gr[x] + fma4(-c2, rr[x], c1 * ww[x]);
-        gw[x] = fma4(c1, rr[x], gw[x]);
-        if (lane == 0) part[1] += dot * dot / nr;
-      }
-      if (a.regs & 4) {               // normLoss(rel rows)
-        const float s = group_sum<GL>(dot4(rr[x], rr[x]));
-        if (s - 1.f > 0.f) gr[x] = fma4(2.f * g1, rr[x], gr[x]);
-        if (lane == 0) part[3] += fmaxf(s - 1.f, 0.f);
-      }
-    }
+    float4 ge[4], gr[2], gw[2];          // jTransUP.py:144-157 = transH.py:58-71; TransE: transE.py:51-63
+    kg_pair_math<GL, TRANSH>(t.e, rr, ww, a.l1, a.margin, a.gscale, a.regs, lane, part, ge, gr, gw);
     if (on) {
 #pragma unroll
       for (int x = 0; x < 2; ++x)
@@ -257,19 +201,14 @@ __global__ __launch_bounds__(256) void kg_step_rows_kernel(KgRowsArgs a) {
 
 template <bool TRANSH>
 int launch_kg_rows(KgRowsArgs& a, hipStream_t st, const char* name) {
-#define KTUP_KGR(GL)                                                                                            \
-  {                                                                                                             \
-    constexpr int GPB = 256 / GL;                                                                               \
-    int64_t ch = a.B / ((int64_t)GPB * 512);                                                                    \
-    a.chunk = (int)(ch < 1 ? 1 : ch > 16 ? 16 : ch);                                                            \
-    const int64_t grid = (a.B + (int64_t)GPB * a.chunk - 1) / ((int64_t)GPB * a.chunk);                         \
-    hipLaunchKernelGGL((kg_step_rows_kernel<GL, TRANSH>), dim3((unsigned)grid), dim3(256), 0, st, a);           \
-    return check_launch(name);                                                                                  \
-  }
-  if (a.nch <= 16) KTUP_KGR(16)
-  if (a.nch <= 32) KTUP_KGR(32)
-  KTUP_KGR(64)
-#undef KTUP_KGR
+  return with_lane_group(a.nch, [&](auto gl) {
+    constexpr int GPB = 256 / decltype(gl)::value;
+    const int64_t ch = a.B / ((int64_t)GPB * 512);
+    a.chunk = (int)(ch < 1 ? 1 : ch > 16 ? 16 : ch);
+    const int64_t grid = (a.B + (int64_t)GPB * a.chunk - 1) / ((int64_t)GPB * a.chunk);
+    hipLaunchKernelGGL((kg_step_rows_kernel<decltype(gl)::value, TRANSH>), dim3((unsigned)grid), dim3(256), 0, st, a);
+    return check_launch(name);
+  });
 }
 
 }  // namespace
@@ -290,8 +229,7 @@ extern "C" int ktup_train_kg_step_rows(int transh, const float* E, int64_t lde, 
   KTUP_REQUIRE(B >= 0, "%s: negative batch", name);
   if (B == 0) return KTUP_OK;
   KTUP_REQUIRE(E && R && ent_ids && rel_ids && loss && GE && gR && (!transh || (Nrm && gN)), "%s: null pointer argument", name);
-  if (d <= 0 || d % 4 || d > 256 || (lde | ldr | (transh ? ldn : 0)) % 4 || !aligned16(E) || !aligned16(R) || !aligned16(GE) || !aligned16(gR) ||
-      (transh && (!aligned16(Nrm) || !aligned16(gN))))
+  if (!lane_group_rows_ok(d, {lde, ldr, transh ? ldn : 0}, {E, R, GE, gR, transh ? Nrm : nullptr, transh ? gN : nullptr}))
     return set_error(KTUP_ERR_UNSUPPORTED, "%s: needs d %% 4 == 0 (<= 256) and 16-byte aligned rows", name);
   KgRowsArgs a{E, R, Nrm, lde, ldr, ldn, ent_ids, ent_pad, rel_ids, order, B, d / 4, l1 != 0, margin, gscale, regs, 1, loss, GE, gR, gN, sumsq, n_slots};
   return transh ? launch_kg_rows<true>(a, (hipStream_t)stream, name) : launch_kg_rows<false>(a, (hipStream_t)stream, name);

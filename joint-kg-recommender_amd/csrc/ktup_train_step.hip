@@ -10,7 +10,10 @@
 //                                                                              -> kg_step_kernel below
 // A lane group owns pair k = the positive triple k and its corrupted twin: both scores, the margin term, both backward passes
 // and the regulariser terms of the rows it has in registers anyway (the reference re-gathers them through second nn.Embedding
-// lookups); each gathered row receives ONE float4 atomic per chunk carrying the sum of all its contributions.
+// lookups); each gathered row receives ONE float4 atomic per chunk carrying the sum of all its contributions.  The pair's arithmetic
+// (kg_pair_math), the walk over the pairs, the scatter's tracked and plain form and the workgroup tail are ktup_kg_pair.h's, shared with
+// kg_step_rows_kernel (ktup_shard_kg.hip) and transd_step_kernel (ktup_transd_step.hip); kg_step_kernel keeps its loads and its scatter list.
+#include "ktup_kg_pair.h"
 #include "ktup_rows.h"
 #include "ktup_pref_geom.h"
 
@@ -27,23 +30,19 @@ struct KgStepArgs {
   float* loss;                   // [4]: margin sum, orth, normE, normR  (accumulated)
   float *gE, *gR, *gN;
   double* gnorm;                 // (may be null) the gradient-norm workspace of ktup_common.h: every add tracks the squared norm it builds
-  int serial;                    // option `deterministic`: ONE lane group of one workgroup walks every pair, so that each gradient cell receives its
-                                 // adds in program order (the sums of float atomics from several waves depend on the order they land in)
+  int serial;                    // option `deterministic`: one lane group of one workgroup walks every pair (PairWalk)
 };
 
 template <int GL, bool TRANSH>
 __global__ __launch_bounds__(256) void kg_step_kernel(KgStepArgs a) {
-  constexpr int GPB = 256 / GL;
   const int lane = threadIdx.x % GL;
   const bool on = lane < a.nch;
   float part[4] = {0.f, 0.f, 0.f, 0.f};
-  const float g1 = a.gscale;
   const bool track = a.gnorm != nullptr;
   const int gset = track ? gnorm_set(a.gnorm) : 0;
   float ssq = 0.f;
-  const int64_t k0 = a.serial ? (threadIdx.x < GL ? 0 : a.B) : (int64_t)blockIdx.x * GPB + threadIdx.x / GL;
-  const int64_t kstep = a.serial ? 1 : (int64_t)gridDim.x * GPB;
-  for (int64_t k = k0; k < a.B; k += kstep) {
+  const PairWalk<GL> walk(a.serial, a.B);
+  for (int64_t k = walk.k0; k < a.B; k += walk.step) {
     const int64_t id[4] = {a.h[k], a.t[k], a.h[k + a.B], a.t[k + a.B]};      // ph, pt, nh, nt
     const int64_t rid[2] = {a.r[k], a.r[k + a.B]};
     float4 e[4], rr[2], ww[2];
@@ -54,123 +53,38 @@ __global__ __launch_bounds__(256) void kg_step_kernel(KgStepArgs a) {
       rr[x] = on ? reinterpret_cast<const float4*>(a.R + rid[x] * a.ldr)[lane] : f4zero();
       ww[x] = (TRANSH && on) ? reinterpret_cast<const float4*>(a.Nm + rid[x] * a.ldn)[lane] : f4zero();
     }
-    // ---- forward of both triples (transH.py:58-71 / transE.py:51-63)
-    float dh[2] = {0.f, 0.f}, dt[2] = {0.f, 0.f}, sc[2];
-    float4 z[2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-      const float4 hh = e[2 * x], tt = e[2 * x + 1];
-      if (TRANSH) {
-        dh[x] = group_sum<GL>(dot4(hh, ww[x]));
-        dt[x] = group_sum<GL>(dot4(tt, ww[x]));
-        const float4 ph = fma4(-dh[x], ww[x], hh), pt = fma4(-dt[x], ww[x], tt);
-        z[x] = (ph + rr[x]) - pt;
-      } else {
-        z[x] = (hh + rr[x]) - tt;
-      }
-      sc[x] = group_sum<GL>(dist4(z[x], a.l1));
-    }
-    // ---- marginLoss (utils/loss.py:8-16): sum_k max(pos - neg + margin, 0)
-    const float diff = sc[0] - sc[1];
-    const bool act = diff + a.margin > 0.f;
-    if (lane == 0) part[0] += fmaxf(diff + a.margin, 0.f);
-    const float gs[2] = {act ? g1 : 0.f, act ? -g1 : 0.f};
-    // ---- backward of both triples + the regularisers of the rows in registers
     float4 ge[4], gr[2], gw[2];
+    kg_pair_math<GL, TRANSH>(e, rr, ww, a.l1, a.margin, a.gscale, a.regs, lane, part, ge, gr, gw);
+    auto scatter = [&](auto add) {    // one float4 atomic per gathered row and chunk
+      RowAdded oe[4], orr[2], ow[2];
 #pragma unroll
-    for (int x = 0; x < 2; ++x) {
-      const float4 gz = gs[x] * ddist4(z[x], a.l1);
-      if (TRANSH) {
-        const float aw = group_sum<GL>(dot4(gz, ww[x]));
-        const float sq = dh[x] - dt[x];
-        const float4 q = e[2 * x] - e[2 * x + 1];
-        ge[2 * x] = fma4(-aw, ww[x], gz);                          // gh
-        ge[2 * x + 1] = -1.f * ge[2 * x];                          // gt
-        gw[x] = fma4(-aw, q, (-sq) * gz);                          // gw
-      } else {
-        ge[2 * x] = gz;
-        ge[2 * x + 1] = -1.f * gz;
-        gw[x] = f4zero();
-      }
-      gr[x] = gz;
-    }
-    if (a.regs & 2) {                 // normLoss(ent rows): sum max(|x|^2 - 1, 0)  (utils/loss.py:21-23)
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const float s = group_sum<GL>(dot4(e[x], e[x]));
-        if (s - 1.f > 0.f) ge[x] = fma4(2.f * g1, e[x], ge[x]);
-        if (lane == 0) part[2] += fmaxf(s - 1.f, 0.f);
-      }
-    }
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-      if (TRANSH && (a.regs & 1)) {   // orthogonalLoss(rel rows, norm rows): sum (w.r)^2 / |r|^2  (utils/loss.py:18-19)
-        const float dot = group_sum<GL>(dot4(rr[x], ww[x])), nr = group_sum<GL>(dot4(rr[x], rr[x]));
-        const float c1 = g1 * 2.f * dot / nr, c2 = g1 * 2.f * dot * dot / (nr * nr);
-        gr[x] = gr[x] + fma4(-c2, rr[x], c1 * ww[x]);
-        gw[x] = fma4(c1, rr[x], gw[x]);
-        if (lane == 0) part[1] += dot * dot / nr;
-      }
-      if (a.regs & 4) {               // normLoss(rel rows)
-        const float s = group_sum<GL>(dot4(rr[x], rr[x]));
-        if (s - 1.f > 0.f) gr[x] = fma4(2.f * g1, rr[x], gr[x]);
-        if (lane == 0) part[3] += fmaxf(s - 1.f, 0.f);
-      }
-    }
-    if (on && track) {                // every add issued before the first returned value is used (ktup_common.h)
-      float4 oe[4], orr[2], ow[2];
-#pragma unroll
-      for (int x = 0; x < 4; ++x) oe[x] = atomic_add4_old(a.gE + id[x] * a.lde + 4 * lane, ge[x]);
+      for (int x = 0; x < 4; ++x) oe[x] = add(a.gE + id[x] * a.lde + 4 * lane, ge[x]);
 #pragma unroll
       for (int x = 0; x < 2; ++x) {
-        orr[x] = atomic_add4_old(a.gR + rid[x] * a.ldr + 4 * lane, gr[x]);
-        ow[x] = TRANSH ? atomic_add4_old(a.gN + rid[x] * a.ldn + 4 * lane, gw[x]) : f4zero();
+        orr[x] = add(a.gR + rid[x] * a.ldr + 4 * lane, gr[x]);
+        ow[x] = add(a.gN + rid[x] * a.ldn + 4 * lane, gw[x], TRANSH);
       }
+      if (add.track) {
 #pragma unroll
-      for (int x = 0; x < 4; ++x) ssq += sq_gain4(oe[x], ge[x]);
+        for (int x = 0; x < 4; ++x) ssq += gain(oe[x]);
 #pragma unroll
-      for (int x = 0; x < 2; ++x) ssq += sq_gain4(orr[x], gr[x]) + (TRANSH ? sq_gain4(ow[x], gw[x]) : 0.f);
-    } else if (on) {
-#pragma unroll
-      for (int x = 0; x < 4; ++x) atomic_add4(a.gE + id[x] * a.lde + 4 * lane, ge[x]);
-#pragma unroll
-      for (int x = 0; x < 2; ++x) {
-        atomic_add4(a.gR + rid[x] * a.ldr + 4 * lane, gr[x]);
-        if (TRANSH) atomic_add4(a.gN + rid[x] * a.ldn + 4 * lane, gw[x]);
+        for (int x = 0; x < 2; ++x) ssq += gain(orr[x]) + gain(ow[x]);
       }
-    }
+    };
+    if (on && track) scatter(RowAdd<true>{});
+    else if (on) scatter(RowAdd<false>{});
   }
-  // ---- the four loss values: wave sums -> one atomic per workgroup and slot
-  __shared__ float red[4][5];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const float v = group_sum<64>(part[s]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][s] = v;
-  }
-  if (track) {
-    ssq = group_sum<64>(ssq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][4] = ssq;
-  }
-  __syncthreads();
-  if (track && threadIdx.x == 64) gnorm_add(a.gnorm, gset, ((double)red[0][4] + (double)red[1][4]) + ((double)red[2][4] + (double)red[3][4]));
-  if (threadIdx.x < 4) {
-    const float v = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    if (v != 0.f) atomicAdd(a.loss + threadIdx.x, v);
-  }
+  step_tail(part, ssq, a.gnorm, gset, a.loss);
 }
 
 template <bool TRANSH>
 int launch_kg(const KgStepArgs& a, hipStream_t st, const char* name) {
-#define KTUP_KG(GL)                                                                                            \
-  {                                                                                                            \
-    const int grid = a.serial ? 1 : grid_for((a.B + (256 / GL) - 1) / (256 / GL), 1024);                       \
-    hipLaunchKernelGGL((kg_step_kernel<GL, TRANSH>), dim3(grid), dim3(256), 0, st, a);                         \
-    return check_launch(name);                                                                                 \
-  }
-  if (a.nch <= 16) KTUP_KG(16)
-  if (a.nch <= 32) KTUP_KG(32)
-  KTUP_KG(64)
-#undef KTUP_KG
+  return with_lane_group(a.nch, [&](auto gl) {
+    constexpr int GPB = 256 / decltype(gl)::value;
+    const int grid = a.serial ? 1 : grid_for((a.B + GPB - 1) / GPB, 1024);
+    hipLaunchKernelGGL((kg_step_kernel<decltype(gl)::value, TRANSH>), dim3(grid), dim3(256), 0, st, a);
+    return check_launch(name);
+  });
 }
 
 // ---- the row regularisers of TUP's rec step (item_recommendation.py:177-180) for a step whose row gradients are STORED per pair
@@ -234,20 +148,16 @@ extern "C" int ktup_train_rec_reg_rows(const float* U, int64_t ldu, const float*
   KTUP_REQUIRE(B >= 0 && n_pref >= 0, "%s: negative sizes", name);
   if (B == 0 && n_pref == 0) return KTUP_OK;
   KTUP_REQUIRE(U && I && u_ids && i_ids && GU && GV && loss && (n_pref == 0 || (pref && gP)), "%s: null pointer argument", name);
-  if (d % 4 || d > 256 || (ldu | ldi) % 4 || !aligned16(U) || !aligned16(I) || !aligned16(GU) || !aligned16(GV) || !aligned16(pref) || !aligned16(gP))
+  if (!lane_group_rows_ok(d, {ldu, ldi}, {U, I, GU, GV, pref, gP}))
     return set_error(KTUP_ERR_UNSUPPORTED, "%s: needs d %% 4 == 0 (<= 256) and 16-byte aligned rows", name);
   RegRowsArgs a{U, I, ldu, ldi, d / 4, u_ids, i_ids, B, GU, GV, (int64_t)d, pref, n_pref, gP, scale_rows, scale_pref, loss};
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = 3 * B + n_pref;
-#define KTUP_RR(GL)                                                                                                  \
-  {                                                                                                                  \
-    hipLaunchKernelGGL((reg_rows_kernel<GL>), dim3(grid_for((total + (256 / GL) - 1) / (256 / GL), 2048)), dim3(256), 0, st, a); \
-    return check_launch(name);                                                                                       \
-  }
-  if (a.nch <= 16) KTUP_RR(16)
-  if (a.nch <= 32) KTUP_RR(32)
-  KTUP_RR(64)
-#undef KTUP_RR
+  return with_lane_group(a.nch, [&](auto gl) {
+    constexpr int GPB = 256 / decltype(gl)::value;
+    hipLaunchKernelGGL((reg_rows_kernel<decltype(gl)::value>), dim3(grid_for((total + GPB - 1) / GPB, 2048)), dim3(256), 0, st, a);
+    return check_launch(name);
+  });
 }
 
 // 1 = this (step kind, d, n_pref) has a fused kernel; 0 = keep the multi-launch step.  kind: 0 rec (TUP / KTUP), 1 kg TransH, 2 kg TransE
@@ -338,8 +248,7 @@ extern "C" int ktup_train_kg_step(int transh, const float* E, int64_t lde, const
   KTUP_REQUIRE(B >= 0 && (B > 0 || !gnorm), "%s: negative batch (or an empty one with a tracked norm)", name);
   if (B == 0) return KTUP_OK;
   KTUP_REQUIRE(E && R && h && t && r && loss && gE && gR && (!transh || (Nrm && gN)), "%s: null pointer argument", name);
-  if (d <= 0 || d % 4 || d > 256 || (lde | ldr | (transh ? ldn : 0)) % 4 || !aligned16(E) || !aligned16(R) || !aligned16(gE) || !aligned16(gR) ||
-      (transh && (!aligned16(Nrm) || !aligned16(gN))))
+  if (!lane_group_rows_ok(d, {lde, ldr, transh ? ldn : 0}, {E, R, gE, gR, transh ? Nrm : nullptr, transh ? gN : nullptr}))
     return set_error(KTUP_ERR_UNSUPPORTED, "%s: needs d %% 4 == 0 (<= 256) and 16-byte aligned rows", name);
   KgStepArgs a{E, R, Nrm, lde, ldr, ldn, h, t, r, B, d / 4, l1 != 0, margin, gscale, regs, loss, gE, gR, gN, gnorm, opt_deterministic() != 0};
   return transh ? launch_kg<true>(a, (hipStream_t)stream, name) : launch_kg<false>(a, (hipStream_t)stream, name);

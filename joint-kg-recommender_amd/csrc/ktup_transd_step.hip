@@ -1,5 +1,6 @@
-// The TransD training step of the KG driver as ONE launch (knowledge_representation.py:176-204 with transD.py:61-76): a sibling of
-// kg_step_kernel (ktup_train_step.hip) with two more tables.  A lane group owns example k = the positive triple k and its corrupted
+// The TransD training step of the KG driver as ONE launch (knowledge_representation.py:176-204 with transD.py:61-76): built from
+// the parts of ktup_kg_pair.h that kg_step_kernel (ktup_train_step.hip) is built from -- the walk over the examples, normLoss over rows in
+// registers, the scatter's two forms, the workgroup tail -- around its own arithmetic on two more tables.  A lane group owns example k = the positive triple k and its corrupted
 // twin k + B and holds their twelve rows (h, t, h_p, t_p, r, r_p of each; the twin's relation may differ) in registers as float4:
 //   alpha = h . h_p,  beta = t . t_p,  v = (h + alpha r_p) + r - (t + beta r_p),  s = sum |v| or sum v^2       (ktup_score_transd_fwd)
 //   marginLoss: sum_k max(s+ - s- + margin, 0);  normLoss(entity rows), normLoss(relation rows) from the rows in registers
@@ -8,7 +9,7 @@
 // Each gathered row receives one float4 atomic per chunk with the sum of its contributions; a row that receives nothing (an inactive
 // example's projection rows, its entity and relation rows unless their regulariser fires) gets no atomic at all.  Ep and Rp carry no
 // regulariser (knowledge_representation.py:200-204).
-#include "ktup_common.h"
+#include "ktup_kg_pair.h"
 
 using namespace ktup;
 
@@ -23,22 +24,20 @@ struct TdStepArgs {
   float* loss;                   // [4]: margin sum, (unused), normE, normR  (accumulated)
   float *gE, *gR, *gEp, *gRp;
   double* gnorm;                 // (may be null) the gradient-norm workspace of ktup_common.h
-  int serial;                    // option `deterministic`: one lane group of one workgroup walks every example (kg_step_kernel)
+  int serial;                    // option `deterministic`: one lane group of one workgroup walks every example (PairWalk)
 };
 
 template <int GL>
 __global__ __launch_bounds__(256) void transd_step_kernel(TdStepArgs a) {
-  constexpr int GPB = 256 / GL;
   const int lane = threadIdx.x % GL;
   const bool on = lane < a.nch;
-  float part[4] = {0.f, 0.f, 0.f, 0.f};
+  float part[4] = {0.f, 0.f, 0.f, 0.f};       // slot 1 (orthogonalLoss) stays 0 and is never written
   const float g1 = a.gscale;
   const bool track = a.gnorm != nullptr;
   const int gset = track ? gnorm_set(a.gnorm) : 0;
   float ssq = 0.f;
-  const int64_t k0 = a.serial ? (threadIdx.x < GL ? 0 : a.B) : (int64_t)blockIdx.x * GPB + threadIdx.x / GL;
-  const int64_t kstep = a.serial ? 1 : (int64_t)gridDim.x * GPB;
-  for (int64_t k = k0; k < a.B; k += kstep) {
+  const PairWalk<GL> walk(a.serial, a.B);
+  for (int64_t k = walk.k0; k < a.B; k += walk.step) {
     const int64_t id[4] = {a.h[k], a.t[k], a.h[k + a.B], a.t[k + a.B]};      // ph, pt, nh, nt
     const int64_t rid[2] = {a.r[k], a.r[k + a.B]};
     float4 e[4], ep[4], rr[2], rp[2];
@@ -82,88 +81,47 @@ __global__ __launch_bounds__(256) void transd_step_kernel(TdStepArgs a) {
       gr[x] = g;
       grp[x] = ab[x] * g;
     }
-    if (a.regs & 2) {                 // normLoss(ent rows): sum max(|x|^2 - 1, 0)  (utils/loss.py:21-23)
+    if (a.regs & 2) norm_loss_rows<GL>(e, g1, lane, part[2], ge, he);
+    if (a.regs & 4) norm_loss_rows<GL>(rr, g1, lane, part[3], gr, hr);
+    auto scatter = [&](auto add) {    // a row that receives nothing gets no atomic
+      RowAdded oe[4], oep[4], orr[2], orp[2];
 #pragma unroll
       for (int x = 0; x < 4; ++x) {
-        const float s = group_sum<GL>(dot4(e[x], e[x]));
-        if (s - 1.f > 0.f) { ge[x] = fma4(2.f * g1, e[x], ge[x]); he[x] = true; }
-        if (lane == 0) part[2] += fmaxf(s - 1.f, 0.f);
-      }
-    }
-    if (a.regs & 4) {                 // normLoss(rel rows)
-#pragma unroll
-      for (int x = 0; x < 2; ++x) {
-        const float s = group_sum<GL>(dot4(rr[x], rr[x]));
-        if (s - 1.f > 0.f) { gr[x] = fma4(2.f * g1, rr[x], gr[x]); hr[x] = true; }
-        if (lane == 0) part[3] += fmaxf(s - 1.f, 0.f);
-      }
-    }
-    if (on && track) {                // every add issued before the first returned value is used (ktup_common.h)
-      float4 oe[4], oep[4], orr[2], orp[2];
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        oe[x] = he[x] ? atomic_add4_old(a.gE + id[x] * a.lde + 4 * lane, ge[x]) : f4zero();
-        oep[x] = act ? atomic_add4_old(a.gEp + id[x] * a.ldep + 4 * lane, gep[x]) : f4zero();
+        oe[x] = add(a.gE + id[x] * a.lde + 4 * lane, ge[x], he[x]);
+        oep[x] = add(a.gEp + id[x] * a.ldep + 4 * lane, gep[x], act);
       }
 #pragma unroll
       for (int x = 0; x < 2; ++x) {
-        orr[x] = hr[x] ? atomic_add4_old(a.gR + rid[x] * a.ldr + 4 * lane, gr[x]) : f4zero();
-        orp[x] = act ? atomic_add4_old(a.gRp + rid[x] * a.ldrp + 4 * lane, grp[x]) : f4zero();
+        orr[x] = add(a.gR + rid[x] * a.ldr + 4 * lane, gr[x], hr[x]);
+        orp[x] = add(a.gRp + rid[x] * a.ldrp + 4 * lane, grp[x], act);
       }
+      if (add.track) {
 #pragma unroll
-      for (int x = 0; x < 4; ++x) ssq += (he[x] ? sq_gain4(oe[x], ge[x]) : 0.f) + (act ? sq_gain4(oep[x], gep[x]) : 0.f);
+        for (int x = 0; x < 4; ++x) ssq += gain(oe[x]) + gain(oep[x]);
 #pragma unroll
-      for (int x = 0; x < 2; ++x) ssq += (hr[x] ? sq_gain4(orr[x], gr[x]) : 0.f) + (act ? sq_gain4(orp[x], grp[x]) : 0.f);
-    } else if (on) {
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        if (he[x]) atomic_add4(a.gE + id[x] * a.lde + 4 * lane, ge[x]);
-        if (act) atomic_add4(a.gEp + id[x] * a.ldep + 4 * lane, gep[x]);
+        for (int x = 0; x < 2; ++x) ssq += gain(orr[x]) + gain(orp[x]);
       }
-#pragma unroll
-      for (int x = 0; x < 2; ++x) {
-        if (hr[x]) atomic_add4(a.gR + rid[x] * a.ldr + 4 * lane, gr[x]);
-        if (act) atomic_add4(a.gRp + rid[x] * a.ldrp + 4 * lane, grp[x]);
-      }
-    }
+    };
+    if (on && track) scatter(RowAdd<true>{});
+    else if (on) scatter(RowAdd<false>{});
   }
-  // ---- the loss values: wave sums -> one atomic per workgroup and slot (slot 1 stays 0 and is never written)
-  __shared__ float red[4][5];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const float w = group_sum<64>(part[s]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][s] = w;
-  }
-  if (track) {
-    ssq = group_sum<64>(ssq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][4] = ssq;
-  }
-  __syncthreads();
-  if (track && threadIdx.x == 64) gnorm_add(a.gnorm, gset, ((double)red[0][4] + (double)red[1][4]) + ((double)red[2][4] + (double)red[3][4]));
-  if (threadIdx.x < 4) {
-    const float w = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    if (w != 0.f) atomicAdd(a.loss + threadIdx.x, w);
-  }
+  step_tail(part, ssq, a.gnorm, gset, a.loss);
 }
 
 int launch_transd(const TdStepArgs& a, hipStream_t st, const char* name) {
-#define KTUP_TDS(GL)                                                                                           \
-  {                                                                                                            \
-    const int grid = a.serial ? 1 : grid_for((a.B + (256 / GL) - 1) / (256 / GL), 1024);                       \
-    hipLaunchKernelGGL((transd_step_kernel<GL>), dim3(grid), dim3(256), 0, st, a);                             \
-    return check_launch(name);                                                                                 \
-  }
-  if (a.nch <= 16) KTUP_TDS(16)
-  if (a.nch <= 32) KTUP_TDS(32)
-  KTUP_TDS(64)
-#undef KTUP_TDS
+  return with_lane_group(a.nch, [&](auto gl) {
+    constexpr int GPB = 256 / decltype(gl)::value;
+    const int grid = a.serial ? 1 : grid_for((a.B + GPB - 1) / GPB, 1024);
+    hipLaunchKernelGGL((transd_step_kernel<decltype(gl)::value>), dim3(grid), dim3(256), 0, st, a);
+    return check_launch(name);
+  });
 }
 
 }  // namespace
 
 #define KTUP_TDS_NONNULL(p) KTUP_REQUIRE((p) != nullptr, "%s: null pointer argument '" #p "'", name)
 
-extern "C" int ktup_train_transd_step_supported(int d) { return d >= 1 && d <= 256 && d % 4 == 0; }
+extern "C" int ktup_train_transd_step_supported(int d) { return lane_group_rows_ok(d, {}, {}); }
 
 extern "C" int ktup_train_transd_step(const float* E, int64_t lde, const float* R, int64_t ldr, const float* Ep, int64_t ldep,
                                       const float* Rp, int64_t ldrp, int d, const int64_t* h, const int64_t* t, const int64_t* r,
@@ -178,8 +136,7 @@ extern "C" int ktup_train_transd_step(const float* E, int64_t lde, const float* 
   KTUP_TDS_NONNULL(E); KTUP_TDS_NONNULL(R); KTUP_TDS_NONNULL(Ep); KTUP_TDS_NONNULL(Rp);
   KTUP_TDS_NONNULL(h); KTUP_TDS_NONNULL(t); KTUP_TDS_NONNULL(r); KTUP_TDS_NONNULL(loss);
   KTUP_TDS_NONNULL(gE); KTUP_TDS_NONNULL(gR); KTUP_TDS_NONNULL(gEp); KTUP_TDS_NONNULL(gRp);
-  if (!ktup_train_transd_step_supported(d) || (lde | ldr | ldep | ldrp) % 4 || !aligned16(E) || !aligned16(R) || !aligned16(Ep) || !aligned16(Rp) ||
-      !aligned16(gE) || !aligned16(gR) || !aligned16(gEp) || !aligned16(gRp))
+  if (!lane_group_rows_ok(d, {lde, ldr, ldep, ldrp}, {E, R, Ep, Rp, gE, gR, gEp, gRp}))
     return set_error(KTUP_ERR_UNSUPPORTED, "%s: needs d %% 4 == 0 (<= 256; got %d) and 16-byte aligned tables and gradients with pitches that are "
                      "multiples of 4 floats (see ktup_train_transd_step_supported)", name, d);
   TdStepArgs a{E, R, Ep, Rp, lde, ldr, ldep, ldrp, h, t, r, B, d / 4, l1 != 0, margin, gscale, regs, loss, gE, gR, gEp, gRp, gnorm,

@@ -26,7 +26,8 @@ rounded up to 4, 5 or 8: P 1, 16 -> 4; 17, 20 -> 5; 21, 32 -> 8; kg: lane-group 
   test_rec_reg_rows               reg_rows_kernel at group widths 16 (d 64), 32 (d 100), 64 (d 256)
   test_kg_step_shapes             d 4 (GL 16), 20 (16), 36 (16), 64 (16), 100 (32), 128 (32), 132 (64), 256 (64) x TransE/TransH
   test_kg_step_regs_and_margin, _options, _exact_zero, _tracked_norm, _grid_stride, _deterministic     the same kernels
-  test_kg_rows                    kg_step_rows_kernel at GL 16 (d 36), 32 (d 100), 64 (d 256) x TransE/TransH"""
+  test_kg_rows                    kg_step_rows_kernel at GL 16 (d 36), 32 (d 100), 64 (d 256) x TransE/TransH
+  test_kg_rows_regs               the same kernel at GL 16 with no regulariser and each one alone (regs 0, 1, 2, 4)"""
 import pytest
 import torch
 
@@ -513,16 +514,10 @@ def test_kg_step_deterministic(transh, l1):
             kg_check(R.kg_case(d, 67, transh, l1, seed_of(d, transh, l1, 26), family='kg stride'))
 
 
-@pytest.mark.parametrize('mark', ['minus one', 'ent_pad'])
-@pytest.mark.parametrize('ordered', [False, True])
-@pytest.mark.parametrize('transh,l1', MODELS)
-@pytest.mark.parametrize('d', [36, 100, 256])
-def test_kg_rows(d, transh, l1, ordered, mark):
-    """ktup_train_kg_step_rows: the 4B entity-row gradients STORED (the buffer starts at a sentinel and a twin's kept end, marked -1
-    or ent_pad, stays unwritten: its gradient is in the positive's row), gR / gN accumulated, with and without the relation order."""
+def kg_rows_check(d, transh, l1, ordered, mark, regs):
     B = 17
     c = R.kg_case(d, B, transh, l1, seed_of(d, transh, l1, 27), family='kg rows')
-    loss, GE, written, small, sumsq = R.kg_rows_reference(c, 1.0, 0.5, 7)
+    loss, GE, written, small, sumsq = R.kg_rows_reference(c, 1.0, 0.5, regs)
     dev, b = kg_device(c), kg_buffers(c)
     pad = c['ne'] + 5                                               # an id no row has
     ent = R.kg_rows_ids(c, -1 if mark == 'minus one' else pad).to(DEV)
@@ -537,7 +532,7 @@ def test_kg_rows(d, transh, l1, ordered, mark):
     ss = torch.zeros(4, dtype=torch.float64, device=DEV)
     th = c['transh']
     lib().call('ktup_train_kg_step_rows', int(th), p(dev['E']), c['lde'], p(dev['R']), c['ldr'], p(dev['N']), c['ldn'] if th else 0, d, p(ent), pad,
-               p(dev['r2']), p(order), B, int(l1), 1.0, 0.5, 7, p(b['loss']), p(dGE), p(b['R']), p(b['N']), p(ss), 4, None)
+               p(dev['r2']), p(order), B, int(l1), 1.0, 0.5, regs, p(b['loss']), p(dGE), p(b['R']), p(b['N']), p(ss), 4, None)
     torch.cuda.synchronize()
     close_loss(b['loss'], loss)
     host = dGE.cpu()
@@ -547,6 +542,24 @@ def test_kg_rows(d, transh, l1, ordered, mark):
     if th:
         close_grad(b['N'], small['N'], 'N')
     close_sum(float(ss.sum()), sumsq, 'sumsq')
+
+
+@pytest.mark.parametrize('mark', ['minus one', 'ent_pad'])
+@pytest.mark.parametrize('ordered', [False, True])
+@pytest.mark.parametrize('transh,l1', MODELS)
+@pytest.mark.parametrize('d', [36, 100, 256])
+def test_kg_rows(d, transh, l1, ordered, mark):
+    """ktup_train_kg_step_rows: the 4B entity-row gradients STORED (the buffer starts at a sentinel and a twin's kept end, marked -1
+    or ent_pad, stays unwritten: its gradient is in the positive's row), gR / gN accumulated, with and without the relation order."""
+    kg_rows_check(d, transh, l1, ordered, mark, 7)
+
+
+@pytest.mark.parametrize('regs', [0, 1, 2, 4])
+@pytest.mark.parametrize('transh,l1', MODELS)
+def test_kg_rows_regs(transh, l1, regs):
+    """The stored-row form with no regulariser and with each one alone (the gating is kg_pair_math's, csrc/ktup_kg_pair.h, which the
+    atomic form shares: test_kg_step_regs_and_margin); a slot whose regulariser is off stays exactly 0 (close_loss)."""
+    kg_rows_check(36, transh, l1, False, 'minus one', regs)
 
 
 def test_redraw_counts_stay_small():
