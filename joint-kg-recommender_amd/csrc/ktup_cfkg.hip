@@ -9,24 +9,14 @@
 // issues ONE row add with contiguous lanes (at most 256 workgroups are launched, whatever B).  The loss partial leaves the same way.
 //
 // cfkg_pass_kernel: the whole rec evaluation pass (CFKG.py:100-118 + the filtered top-n of utils/misc.py:186-248) in one sweep that
-// never writes the (users x candidates) matrix, structured as dot_pass_kernel (ktup_dot_pass.hip): a workgroup owns 64 users
-// (4 waves x 16) and a contiguous split of the candidates; the users' query rows c = U[u] + R[rel] are formed once and held for the
-// pass; candidate rows (gathered through cand_ids) stream through a double-buffered LDS stage whose next contents are in flight under
-// this stage's arithmetic; filter lists are bits, built once per pass; candidates go through pending rows into a sorted list per
-// user (ktup_topn.h), and the splits' lists are merged by topk_merge_kernel.
-//   * squared L2: |c|^2 - 2 c.e + |e|^2 with c.e on v_mfma_f32_16x16x4_f32 (the c rows in registers, one float per lane and 4 k);
-//     |e|^2 is computed once per pass (cfkg_cand_norm_kernel) and rides in the staged row's spare slot;
-//   * L1: on the VALU against the same stage, the wave's 16 query rows in LDS; every lane owns the 4 users x 16-candidate-tile
-//     slots the MFMA would have given it, so the ranking code is one.
-// The spare slot also carries whether the candidate's entity row exists: a cand_ids entry outside [0, n_ent) is never ranked and
-// never dereferenced (the stage reads row 0 in its place).
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "ktup_lane_swap.h"
+// never writes the (users x candidates) matrix.  The sweep is ktup_sweep_pass.h's; cfkg_pass_kernel supplies the scorer: the query
+// row is c = U[u] + R[rel], candidate j is entity row cand_ids[j], and
+//   * squared L2: |c|^2 - 2 c.e + |e|^2 with c.e on v_mfma_f32_16x16x4_f32; |e|^2 is computed once per pass
+//     (cfkg_cand_norm_kernel) and rides in the staged row's spare slot;
+//   * L1: on the VALU against the same stage, the wave's 16 query rows in LDS.
+// The spare slot also carries whether the candidate's entity row exists.
 #include "ktup_rows.h"
-#include "ktup_topn.h"
+#include "ktup_sweep_pass.h"
 
 using namespace ktup;
 
@@ -150,29 +140,10 @@ extern "C" int ktup_train_cfkg_rec_step(const float* U, int64_t ldu, const float
   return check_launch(name);
 }
 
+
 // ================================================================================================ the evaluation pass
 namespace ktup {
 namespace {
-
-constexpr int NSPLIT_MAX = 32;   // candidate splits: NSPLIT_MAX * TOPN_MAX keys per user is what the merge holds, eight per lane
-constexpr int MERGE_PER_LANE = NSPLIT_MAX * TOPN_MAX / 64;
-constexpr size_t WAVE_LDS = (size_t)16 * PCAP * 8 + (size_t)16 * 16 * 8;   // pending rows | lists
-
-// The filter lists of a pass as bits, once per pass: bm[b * words + (j >> 5)] bit (j & 31), one wave per user of u_ids.
-__global__ __launch_bounds__(256) void cfkg_filter_zero_kernel(uint32_t* __restrict__ bm, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) bm[i] = 0u;
-}
-__global__ __launch_bounds__(256) void cfkg_filter_bits_kernel(const int64_t* __restrict__ off, const int32_t* __restrict__ ids, int64_t nq,
-                                                               int64_t n_cand, uint32_t* __restrict__ bm, int64_t words) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); b < nq; b += (int64_t)gridDim.x * 4) {
-    const int64_t f1 = off[b + 1];
-    for (int64_t f = off[b] + lane; f < f1; f += 64) {
-      const int64_t id = ids[f];
-      if (id >= 0 && id < n_cand) atomicOr(bm + b * words + (id >> 5), 1u << (id & 31));
-    }
-  }
-}
 
 // |e|^2 of every candidate, once per pass (squared L2 only): 16 lanes per candidate; a candidate without an entity row gets 0.
 __global__ __launch_bounds__(256) void cfkg_cand_norm_kernel(const float* __restrict__ E, int64_t lde, int64_t n_ent,
@@ -192,200 +163,60 @@ __global__ __launch_bounds__(256) void cfkg_cand_norm_kernel(const float* __rest
 }
 
 struct CfkgPassArgs {
+  SweepArgs sw;
   const float* U; int64_t ldu;
   const float* R; int64_t ldr, rel;
   const float* E; int64_t lde, n_ent;
   const int64_t* cand_ids;              // NULL: candidate j is row j
   const float* enorm;                   // [n_cand] |e|^2 (squared L2); NULL under L1
-  int d, evec;                          // evec: entity rows are whole, 16-byte aligned float4 (else element by element)
-  const int64_t* u_ids; int64_t nq, n_cand;
-  const uint32_t* bm; int64_t bm_words; // the filter bits [nq][bm_words]; NULL = no filter
-  int topn, nsplit; int64_t split_items;
-  uint64_t* part;                       // [nq][nsplit][topn] partial lists
 };
 
-// KS: 4-wide k steps (d <= 4 KS; the padding holds zeros on both sides: it adds nothing to a dot product or to a distance)
+// What cfkg_pass_kernel adds to the sweep.  The sweep ranks s = -distance descending, like the inner-product pass: ascending
+// distance, ties -> lower j.
 template <int KS, bool L1>
-struct CfkgGeom {
-  static constexpr int ST = KS > 32 ? 32 : 64;       // candidates per stage
-  static constexpr int NSUB = ST / 16;               // 16-candidate tiles per stage = accumulators per wave
-  static constexpr int CPR = KS + 1;                 // float4 slots per row: KS operand quads + {|e|^2, row exists, 0, 0}
-  static constexpr int ROW4 = CPR | 1;               // the row's float4 pitch in LDS: odd
-  static constexpr int STG = ST * ROW4;              // float4 per stage buffer
-  static constexpr int SLOTS = ST * KS;              // operand quads a stage loads
-  static constexpr int NPRE = (SLOTS + 255) / 256;   // float4 per thread in flight for the next stage
-  static constexpr int CROW4 = KS | 1;               // L1: float4 pitch of a query row in LDS
-  static constexpr size_t CW = L1 ? (size_t)16 * CROW4 * 16 : 0;   // L1: a wave's 16 query rows
-  static constexpr size_t LDS = (size_t)2 * STG * 16 + 4 * CW + 4 * WAVE_LDS;
-};
-
-template <int KS, bool VEC, bool L1>
-__global__ __launch_bounds__(256, 2) void cfkg_pass_kernel(CfkgPassArgs a) {
-  using G = CfkgGeom<KS, L1>;
-  constexpr int ST = G::ST, NSUB = G::NSUB, ROW4 = G::ROW4, STG = G::STG, SLOTS = G::SLOTS, NPRE = G::NPRE, CROW4 = G::CROW4;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  v4* Xb = reinterpret_cast<v4*>(smem);                                   // [2][STG] candidate stages
-  const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4, j = lane & 15;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* cwf = reinterpret_cast<float*>(smem + (size_t)2 * STG * 16 + (size_t)w * G::CW);   // L1: [16][CROW4] float4, this wave's query rows
-  uint64_t* pbuf = reinterpret_cast<uint64_t*>(smem + (size_t)2 * STG * 16 + 4 * G::CW + (size_t)w * WAVE_LDS);   // [16][PCAP] pending candidates
-  uint64_t* tk = pbuf + 16 * PCAP;                                        // [16][16] the users' sorted lists (touched by merges only)
-  const int64_t ub = (int64_t)(blockIdx.x / (unsigned)a.nsplit);
-  const int sp = (int)(blockIdx.x - (unsigned)ub * (unsigned)a.nsplit);
-  const int64_t u0 = ub * 64 + 16 * w;
-  const int64_t i_lo = (int64_t)sp * a.split_items;
-  const int64_t i_hi = min(a.n_cand, i_lo + a.split_items);
-  const int topn = a.topn, d = a.d;
-  for (int idx = lane; idx < 16 * 16; idx += 64) tk[idx] = PKEY_MAX;
-  // The query rows of the whole pass: lane (kq, j) forms c[user j][4 s + kq] = U[u][.] + R[rel][.] for every k step s
-  float av[KS];
-  {
-    const bool ok = u0 + j < a.nq;
-    const float* urow = a.U + (ok ? a.u_ids[u0 + j] : 0) * a.ldu;
-    const float* rrow = a.R + a.rel * a.ldr;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {                                         // (unconditional, from clamped addresses: all in flight together)
-      const int kk = min(4 * s + kq, d - 1);
-      av[s] = urow[kk] + rrow[kk];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) av[s] = (ok && 4 * s + kq < d) ? av[s] : 0.f;
-  }
+struct CfkgScorer {
+  static constexpr int CROW4 = KS | 1;                                    // L1: float4 pitch of a query row in LDS
+  static constexpr size_t CW = L1 ? (size_t)16 * CROW4 * 16 : 0;          // L1: a wave's 16 query rows
+  static constexpr size_t LDS = 4 * CW;
+  const CfkgPassArgs& a;
   float cn[4] = {0.f, 0.f, 0.f, 0.f};                                     // squared L2: |c|^2 of the users of this lane's accumulator rows
-  if constexpr (L1) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) cwf[(j * CROW4 + s) * 4 + kq] = av[s];   // (read after the workgroup barrier below)
-  } else {
-    float cnj = 0.f;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) cnj = fmaf(av[s], av[s], cnj);
-    cnj += __shfl_xor(cnj, 16, 64);
-    cnj += __shfl_xor(cnj, 32, 64);                                       // |c|^2 of user j on every lane (., j)
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) cn[reg] = __shfl(cnj, 4 * kq + reg, 64);
-  }
-  uint64_t thr[4];                                                        // the users' n-th keys (rows past the end: nothing is ever below)
-  // ... and their NEGATED scores (the sweep ranks s = -distance descending, like the inner-product pass: a value above is a candidate,
-  // one below is not -- one float compare per score; an equal one, a NaN on either side (the threshold of a list that is still
-  // short is one) or a zero of the other sign goes through the 64-bit key compare, so the order is that of the keys in every case)
-  float thrf[4];
-  int pend[4] = {0, 0, 0, 0};
-#pragma unroll
-  for (int reg = 0; reg < 4; ++reg) {
-    const int64_t ur = u0 + 4 * kq + reg;
-    thr[reg] = ur < a.nq ? PKEY_MAX : 0ull;
-    thrf[reg] = ur < a.nq ? __uint_as_float(0x7fffffffu) : __builtin_inff();
-  }
-  // ---- the stage loads: slot e of a stage = operand quad c of candidate r (r = e / KS); candidates past the end re-read the last
-  // one, candidates without an entity row read row 0 (both are masked out below, the operands only have to be there).  Straight-line
-  // code: every load is unconditional from a clamped address, so that all loads of a stage are in flight together.
-  v4 pre[NPRE];
-  float pre_add = 0.f, pre_ok = 0.f;
-  auto cand_row = [&](int64_t c, bool& ok) __attribute__((always_inline)) {
-    const int64_t id = a.cand_ids ? a.cand_ids[c] : c;
-    ok = id >= 0 && id < a.n_ent;
-    return ok ? id : (int64_t)0;
-  };
-  auto fetch = [&](int64_t row0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int k = 0; k < NPRE; ++k) {
-      const int e = min(tid + 256 * k, SLOTS - 1);
-      const int r = e / KS, c = e - r * KS;
-      bool ok;
-      const float* row = a.E + cand_row(min(row0 + r, a.n_cand - 1), ok) * a.lde;
-      if constexpr (VEC) {
-        pre[k] = *reinterpret_cast<const v4*>(row + min(4 * c, d - 4));
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) pre[k][q] = row[min(4 * c + q, d - 1)];
-      }
-    }
-    const int64_t mine = min(row0 + min(tid, ST - 1), a.n_cand - 1);
-    bool ok;
-    (void)cand_row(mine, ok);
-    pre_ok = ok ? 1.f : 0.f;
-    if (a.enorm) pre_add = a.enorm[mine];
-  };
-  auto stash = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-    for (int k = 0; k < NPRE; ++k) {
-      const int e = tid + 256 * k;
-      if (e >= SLOTS) continue;
-      const int r = e / KS, c = e - r * KS;
-      v4 v = pre[k];                                                       // (the padding is zeroed here, not at the load)
-      if (d != 4 * KS) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = 4 * c + q < d ? v[q] : 0.f;
-      }
-      Xb[buf * STG + r * ROW4 + c] = v;
-    }
-    if (tid < ST) Xb[buf * STG + tid * ROW4 + KS] = (v4){pre_add, pre_ok, 0.f, 0.f};
-  };
-  // ---- ranking (see ktup_dot_pass.hip): candidates are appended to the user's pending row in LDS at positions taken from a ballot
-  // (`pend` is replicated over the row's 16 lanes); once a row of a register slot holds 16, that slot's four rows go through the
-  // merge network and the n-th keys are renewed
-  const int rowbase = 16 * kq;
-  const RowAppend app(kq, j);
-  auto flush = [&](bool all) __attribute__((always_inline)) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int n = pend[reg];
-      if (!__builtin_amdgcn_ballot_w64(all ? n > 0 : n >= 16)) continue;
-      const int ur = 4 * kq + reg;
-      const uint64_t* row = pbuf + ur * PCAP;
-      const uint64_t merged = row_merge_pending(tk[ur * 16 + j], row, n, topn, j);   // all four rows of the slot at once
-      tk[ur * 16 + j] = merged;
-      pend[reg] = 0;
-      const uint32_t nhi = (uint32_t)__shfl((int)(uint32_t)(merged >> 32), rowbase + topn - 1, 64);
-      const uint32_t nlo = (uint32_t)__shfl((int)(uint32_t)merged, rowbase + topn - 1, 64);
-      if (u0 + ur < a.nq) {                                                           // (rows past the end keep 0 / +inf)
-        thr[reg] = ((uint64_t)nhi << 32) | nlo;
-        thrf[reg] = -topn_key_score(nhi);                                               // negated (NaN: list short)
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  };
-  // 16 users x the 16 candidates [cand - j, cand - j + 16): acc holds c.e (squared L2) or the distance itself (L1)
-  auto rank_tile = [&](const v4& acc, float en, bool exists, int64_t cand) __attribute__((always_inline)) {
-    const bool iok = cand < i_hi && exists;
-    bool full = false;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int ur = 4 * kq + reg;
-      const float dist = L1 ? acc[reg] : __fadd_rn(fmaf(-2.f, acc[reg], cn[reg]), en);
-      const float s = -dist;
-      const bool above = s > thrf[reg], maybe = !(s < thrf[reg]) && iok;
-      if (!__builtin_amdgcn_ballot_w64(maybe)) continue;                   // most 64-score slots leave here
-      const uint64_t key = topn_key(s, true, (uint32_t)cand);              // (negated back: ascending distance, ties -> lower j)
-      bool c = maybe && (above || key < thr[reg]);
-      if (c && a.bm) c = ((a.bm[(u0 + ur) * a.bm_words + (cand >> 5)] >> (cand & 31)) & 1u) == 0u;
-      const uint64_t m = __builtin_amdgcn_ballot_w64(c);
-      if (m) {
-        app.put(pbuf, ur * PCAP, pend[reg], m, c, [&] { return key; });
-        full |= pend[reg] >= 16;
-      }
-    }
-    if (__builtin_amdgcn_ballot_w64(full)) flush(false);
-  };
-  auto compute = [&](int buf, int64_t row0) __attribute__((always_inline)) {
-    const v4* eb = Xb + buf * STG + j * ROW4;                              // candidate j of tile 0
-    v4 acc[NSUB];
-#pragma unroll
-    for (int t = 0; t < NSUB; ++t) acc[t] = (v4){0.f, 0.f, 0.f, 0.f};
+  const v4* cw = nullptr;                                                 // L1: the query rows of those four users, [4][CROW4]
+  KTUP_DEV float query(int64_t u, int k) const { return a.U[u * a.ldu + k] + a.R[a.rel * a.ldr + k]; }
+  KTUP_DEV void hold(const float (&av)[KS], char* smem, int64_t, const bool (&)[4], int kq, int j) {
     if constexpr (L1) {
-      const v4* cw = reinterpret_cast<const v4*>(cwf) + 4 * kq * CROW4;    // the four users of this lane's accumulator rows
+      float* cwf = reinterpret_cast<float*>(smem + (size_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * CW);   // [16][CROW4] float4
+#pragma unroll
+      for (int s = 0; s < KS; ++s) cwf[(j * CROW4 + s) * 4 + kq] = av[s];
+      cw = reinterpret_cast<const v4*>(cwf) + 4 * kq * CROW4;
+    } else {
+      float cnj = 0.f;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) cnj = fmaf(av[s], av[s], cnj);
+      cnj += __shfl_xor(cnj, 16, 64);
+      cnj += __shfl_xor(cnj, 32, 64);                                     // |c|^2 of user j on every lane (., j)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) cn[reg] = __shfl(cnj, 4 * kq + reg, 64);
+    }
+  }
+  // a cand_ids entry outside [0, n_ent) is never ranked and never dereferenced: the stage reads row 0 in its place
+  KTUP_DEV const float* row(int64_t c, bool& live) const {
+    const int64_t id = a.cand_ids ? a.cand_ids[c] : c;
+    live = id >= 0 && id < a.n_ent;
+    return a.E + (live ? id : (int64_t)0) * a.lde;
+  }
+  KTUP_DEV v4 spare(int64_t c, bool live) const { return (v4){a.enorm ? a.enorm[c] : 0.f, live ? 1.f : 0.f, 0.f, 0.f}; }
+  // acc: c.e on the matrix cores (squared L2), or the distance itself on the VALU against the same stage (L1): every lane owns the
+  // 4 users x 16-candidate-tile slots the MFMA would have given it
+  KTUP_DEV void tile_math(const float (&av)[KS], const v4* eb, int kq, v4 (&acc)[SweepGeom<KS>::NSUB]) const {
+    if constexpr (L1) {
 #pragma unroll 2
       for (int s = 0; s < KS; ++s) {
         v4 cq[4];
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) cq[reg] = cw[reg * CROW4 + s];
 #pragma unroll
-        for (int t = 0; t < NSUB; ++t) {
-          const v4 e = eb[t * 16 * ROW4 + s];
+        for (int t = 0; t < SweepGeom<KS>::NSUB; ++t) {
+          const v4 e = eb[t * 16 * SweepGeom<KS>::ROW4 + s];
 #pragma unroll
           for (int reg = 0; reg < 4; ++reg) {
             const v4 z = cq[reg] - e;
@@ -394,72 +225,27 @@ __global__ __launch_bounds__(256, 2) void cfkg_pass_kernel(CfkgPassArgs a) {
         }
       }
     } else {
-      const float* rb = reinterpret_cast<const float*>(eb) + kq;           // lane (kq, candidate j): element kq of every k quad
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-#pragma unroll
-        for (int t = 0; t < NSUB; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], rb[t * 16 * ROW4 * 4 + 4 * s], acc[t], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < NSUB; ++t) {
-      if (row0 + 16 * t >= i_hi) break;                                    // (uniform)
-      const v4 spare = eb[t * 16 * ROW4 + KS];
-      rank_tile(acc[t], spare[0], spare[1] != 0.f, row0 + 16 * t + j);
-    }
-  };
-  const int64_t nst = (i_hi - i_lo + ST - 1) / ST;
-  fetch(i_lo);
-  stash(0);
-  __syncthreads();                                                         // stage 0, the query rows (L1) and the lists are in place
-  // one stage per workgroup barrier; the next stage's loads are in flight under this stage's arithmetic.  Buffer buf ^ 1 was last read
-  // in the previous iteration, whose closing barrier every wave has passed; its new contents are read after this iteration's barrier.
-  for (int64_t t0 = 0; t0 < nst; ++t0) {
-    const int buf = (int)(t0 & 1);
-    const bool more = t0 + 1 < nst;
-    if (more) fetch(i_lo + (t0 + 1) * ST);
-    __builtin_amdgcn_sched_barrier(0);                                     // the loads are issued before, their values used after the arithmetic
-    compute(buf, i_lo + t0 * ST);
-    __builtin_amdgcn_sched_barrier(0);
-    if (more) stash(buf ^ 1);
-    __syncthreads();
-  }
-  flush(true);
-  if (j < topn) {
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int64_t ur = u0 + 4 * kq + reg;
-      if (ur < a.nq) a.part[(ur * a.nsplit + sp) * topn + j] = tk[(4 * kq + reg) * 16 + j];
+      sweep_tile_dot<KS>(av, eb, kq, acc);
     }
   }
-}
+  KTUP_DEV v4 staged(const v4* slot) const { return *slot; }
+  KTUP_DEV bool live(const v4& spare) const { return spare[1] != 0.f; }
+  KTUP_DEV float score(float acc, int reg, const v4& spare) const {
+    return -(L1 ? acc : __fadd_rn(fmaf(-2.f, acc, cn[reg]), spare[0]));    // |c|^2 - 2 c.e + |e|^2
+  }
+};
 
 template <int KS, bool VEC, bool L1>
-int launch_cfkg_pass_one(const CfkgPassArgs& a, unsigned blocks, hipStream_t st, const char* name) {
-  constexpr size_t lds = CfkgGeom<KS, L1>::LDS;
-  static_assert(lds <= 160 * 1024, "the stages, the query rows and the lists fit the LDS");
-  (void)hipFuncSetAttribute((const void*)cfkg_pass_kernel<KS, VEC, L1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((cfkg_pass_kernel<KS, VEC, L1>), dim3(blocks), dim3(256), lds, st, a);
-  return check_launch(name);
+__global__ __launch_bounds__(256, 2) void cfkg_pass_kernel(CfkgPassArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  CfkgScorer<KS, L1> sc{a};
+  sweep_pass<KS, VEC>(a.sw, sc, smem);
 }
 
-template <int KS>
-int launch_cfkg_pass(const CfkgPassArgs& a, bool l1, unsigned blocks, hipStream_t st, const char* name) {
-  if (l1) return a.evec ? launch_cfkg_pass_one<KS, true, true>(a, blocks, st, name) : launch_cfkg_pass_one<KS, false, true>(a, blocks, st, name);
-  return a.evec ? launch_cfkg_pass_one<KS, true, false>(a, blocks, st, name) : launch_cfkg_pass_one<KS, false, false>(a, blocks, st, name);
-}
-
-// how the candidates are cut: `want` splits, whole 16-candidate tiles each; 0: about 1.25 workgroups per CU (the rule and the
-// measurements of ktup_dot_pass.hip's dot_nsplit).
-int cfkg_nsplit(int64_t nq, int64_t n_cand, int want, int64_t* split_items) {
-  const int64_t nub = (nq + 63) / 64;
-  int64_t ns = want > 0 ? want : (320 + nub - 1) / (nub > 0 ? nub : 1);
-  ns = ns < 1 ? 1 : ns > NSPLIT_MAX ? NSPLIT_MAX : ns;
-  int64_t si = (n_cand + ns - 1) / ns;
-  si = (si + 15) / 16 * 16;
-  if (want <= 0 && si < 256) si = 256;                                     // (a workgroup's prologue wants some candidates to pay for it)
-  *split_items = si;
-  return (int)((n_cand + si - 1) / si);
+template <int KS, bool L1>
+int launch_cfkg_pass(const CfkgPassArgs& a, hipStream_t st, const char* name) {
+  constexpr size_t lds = SweepGeom<KS>::lds(CfkgScorer<KS, L1>::LDS);
+  return a.sw.vec ? sweep_launch<lds>(cfkg_pass_kernel<KS, true, L1>, a, a.sw, st, name) : sweep_launch<lds>(cfkg_pass_kernel<KS, false, L1>, a, a.sw, st, name);
 }
 
 }  // namespace
@@ -467,12 +253,7 @@ int cfkg_nsplit(int64_t nq, int64_t n_cand, int want, int64_t* split_items) {
 
 extern "C" size_t ktup_eval_cfkg_topk_workspace_bytes(int d, int64_t nq, int64_t n_cand, int topn, int nsplit) {
   (void)d;
-  if (nq <= 0 || n_cand <= 0 || topn <= 0 || topn > TOPN_MAX || nsplit < 0) return 0;
-  int64_t si = 0;
-  const int ns = cfkg_nsplit(nq, n_cand, nsplit, &si);
-  const size_t part = (size_t)nq * ns * topn * sizeof(uint64_t);
-  const size_t bits = (size_t)nq * (size_t)((n_cand + 31) / 32) * sizeof(uint32_t);
-  return part + bits + (size_t)n_cand * sizeof(float) + 16;
+  return sweep_workspace_bytes(nq, n_cand, topn, nsplit, 1);
 }
 
 extern "C" int ktup_eval_cfkg_topk(const float* U, int64_t ldu, const float* R, int64_t ldr, int64_t rel, const float* E, int64_t lde,
@@ -496,48 +277,20 @@ extern "C" int ktup_eval_cfkg_topk(const float* U, int64_t ldu, const float* R, 
   if (nq == 0) return KTUP_OK;
   hipStream_t st = (hipStream_t)stream;
   CfkgPassArgs a;
-  a.U = U; a.ldu = ldu; a.R = R; a.ldr = ldr; a.rel = rel; a.E = E; a.lde = lde; a.n_ent = n_ent; a.cand_ids = cand_ids; a.d = d;
-  a.evec = (d % 4 == 0 && lde % 4 == 0 && (reinterpret_cast<uintptr_t>(E) & 15) == 0) ? 1 : 0;
-  a.u_ids = u_ids; a.nq = nq; a.n_cand = n_cand;
-  a.topn = topn;
-  a.nsplit = cfkg_nsplit(nq, n_cand, nsplit, &a.split_items);
-  a.part = reinterpret_cast<uint64_t*>(ws);
-  a.bm = nullptr;
-  a.bm_words = (n_cand + 31) / 32;
-  a.enorm = nullptr;
-  const int64_t nub = (nq + 63) / 64;
-  if (nub * a.nsplit > 0x7fffffffLL) return set_error(KTUP_ERR_UNSUPPORTED, "%s: too many users for one call (%lld)", name, (long long)nq);
-  // workspace: the partial lists (8-byte entries) | the filter bits | |e|^2 per candidate
-  uint32_t* bm = reinterpret_cast<uint32_t*>(a.part + (size_t)nq * a.nsplit * topn);
-  const int64_t nw = nq * a.bm_words;
-  if (filt_off) {
-    hipLaunchKernelGGL(cfkg_filter_zero_kernel, dim3((unsigned)min((nw + 255) / 256, (int64_t)4096)), dim3(256), 0, st, bm, nw);
-    if (int rc = check_launch(name)) return rc;
-    hipLaunchKernelGGL(cfkg_filter_bits_kernel, dim3((unsigned)min((nq + 3) / 4, (int64_t)4096)), dim3(256), 0, st, filt_off, filt_ids, nq, n_cand,
-                       bm, a.bm_words);
-    if (int rc = check_launch(name)) return rc;
-    a.bm = bm;
-  }
+  a.U = U; a.ldu = ldu; a.R = R; a.ldr = ldr; a.rel = rel; a.E = E; a.lde = lde; a.n_ent = n_ent; a.cand_ids = cand_ids; a.enorm = nullptr;
+  a.sw.u_ids = u_ids; a.sw.nq = nq; a.sw.n = n_cand; a.sw.d = d; a.sw.topn = topn;
+  a.sw.vec = (d % 4 == 0 && lde % 4 == 0 && (reinterpret_cast<uintptr_t>(E) & 15) == 0) ? 1 : 0;
+  float* en = nullptr;
+  if (int rc = sweep_prepare(a.sw, nsplit, filt_off, filt_ids, ws, &en, st, name)) return rc;
   if (!l1) {
-    float* en = reinterpret_cast<float*>(bm + nw);
     hipLaunchKernelGGL(cfkg_cand_norm_kernel, dim3((unsigned)min((n_cand + 15) / 16, (int64_t)4096)), dim3(256), 0, st, E, lde, n_ent, cand_ids,
                        n_cand, d, en);
     if (int rc = check_launch(name)) return rc;
     a.enorm = en;
   }
-  const unsigned blocks = (unsigned)(nub * a.nsplit);
-  const int nk = (d + 3) / 4;
-  const bool is_l1 = l1 != 0;
-  int rc;
-  if (nk <= 5) rc = launch_cfkg_pass<5>(a, is_l1, blocks, st, name);
-  else if (nk <= 9) rc = launch_cfkg_pass<9>(a, is_l1, blocks, st, name);
-  else if (nk <= 16) rc = launch_cfkg_pass<16>(a, is_l1, blocks, st, name);
-  else if (nk <= 25) rc = launch_cfkg_pass<25>(a, is_l1, blocks, st, name);
-  else if (nk <= 32) rc = launch_cfkg_pass<32>(a, is_l1, blocks, st, name);
-  else if (nk <= 48) rc = launch_cfkg_pass<48>(a, is_l1, blocks, st, name);
-  else rc = launch_cfkg_pass<64>(a, is_l1, blocks, st, name);
-  if (rc) return rc;
-  hipLaunchKernelGGL((topk_merge_kernel<MERGE_PER_LANE, false>), dim3((unsigned)((nq + 3) / 4)), dim3(MERGE_T), 0, st, a.part, nq, a.nsplit, topn, top_ids,
-                     top_scores);
-  return check_launch(name);
+  const int rc = with_k_steps(d, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    return l1 ? launch_cfkg_pass<KS, true>(a, st, name) : launch_cfkg_pass<KS, false>(a, st, name);
+  });
+  return rc ? rc : sweep_merge<false>(a.sw, top_ids, top_scores, st, name);
 }

@@ -1,5 +1,5 @@
 // The 64-bit ranking key and the 16-lane sorted-list machinery of the evaluation kernels (ktup_rank.hip, ktup_eval.hip,
-// ktup_eval_kg_fused.hip, ktup_eval_pass.hip, ktup_dot_pass.hip).
+// ktup_eval_kg_fused.hip, ktup_eval_pass.hip, and through ktup_sweep_pass.h ktup_dot_pass.hip and ktup_cfkg.hip).
 //        key = (order-preserving image of the fp32 score) << 32 | candidate id
 // so the order is total: ascending score, ties -> lower id first.  A one-sweep pass keeps a user's sorted top-n list (one key per
 // lane of a 16-lane row) in LDS and touches it only when 16 candidates are pending for it; the catalogue splits' partial lists

@@ -498,6 +498,39 @@ def _scratch(nbytes, dev):
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
 
 
+def _no_empty_filter(filt_off, filt_ids):
+    """An empty filter id list has no storage to point at: it means no filter."""
+    if filt_ids is not None and filt_ids.numel() == 0:
+        return None, None
+    return filt_off, filt_ids
+
+
+def _csr_offsets(who, nq, gold_off, filt_off):
+    if gold_off.numel() != nq + 1 or (filt_off is not None and filt_off.numel() != nq + 1):
+        raise L.KtupError('%s: CSR offsets need len(q) + 1 entries' % who)
+
+
+def _input_uniform(uniform, nq, ni, P, dev):
+    if uniform is None or tuple(uniform.shape) != (nq, ni, P) or uniform.dtype != torch.float32 or uniform.device != dev:
+        raise L.KtupError('uniform must be an (n_users, n_items, n_pref) fp32 device tensor')
+    return uniform.contiguous()
+
+
+def _topn_sweep(entry, args, ws_bytes, nq, topn, dev, with_scores, may_decline=True):
+    """The tail of the one-sweep top-n wrappers: entry(*args, top_ids, top_scores, workspace, stream) -> int32 (nq, topn) ids
+    [, scores]; None where the entry point declines the shape with KTUP_ERR_UNSUPPORTED (may_decline: else that raises too)."""
+    top = torch.empty(nq, topn, dtype=torch.int32, device=dev)
+    ts = torch.empty(nq, topn, dtype=torch.float32, device=dev) if with_scores else None
+    ws = _scratch(ws_bytes, dev)
+    try:
+        L.call(entry, *args, _p(top), _p(ts), _p(ws), _stream(dev))
+    except L.KtupError as e:
+        if may_decline and e.code == L.ERR_UNSUPPORTED:
+            return None
+        raise
+    return (top, ts) if with_scores else top
+
+
 @torch.no_grad()
 def eval_bprmf(U, I, u):
     """bprmf.py:51-54 -> (len(u), n_items)."""
@@ -556,10 +589,8 @@ def eval_kg_ranks_transd(E, R, Ep, Rp, q, r, l1, head, descending, gold_off, gol
     """eval_kg_ranks for TransD (ktup_eval_kg_ranks_transd): the score matrix of `chunk` keys at a time + K18, the loop under the C ABI.
     -> int32 [gold_off[-1]]; -1 = a gold id that is itself filtered."""
     nq = q.numel()
-    if filt_ids is not None and filt_ids.numel() == 0:
-        filt_off = filt_ids = None
-    if gold_off.numel() != nq + 1 or (filt_off is not None and filt_off.numel() != nq + 1):      # (a shape check: before anything else)
-        raise L.KtupError('eval_kg_ranks_transd: CSR offsets need len(q) + 1 entries')
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
+    _csr_offsets('eval_kg_ranks_transd', nq, gold_off, filt_off)      # (a shape check: before anything else)
     dev = _dev(_table('entity table', E)); _table('relation table', R)
     _table('entity projection table', Ep); _table('relation projection table', Rp)
     C = E if candidates is None else _table('candidate table', candidates)
@@ -602,10 +633,8 @@ def eval_kg_ranks(E, R, N, q, r, l1, head, descending, gold_off, gold_ids, filt_
         _table('norm table', N)
     C = E if candidates is None else _table('candidate table', candidates)
     nq = q.numel(); q = _ids('q', q, dev); r = _ids('r', r, dev, nq)
-    if filt_ids is not None and filt_ids.numel() == 0:       # an empty id list has no storage to point at: same as no filter
-        filt_off = filt_ids = None
-    if gold_off.numel() != nq + 1 or (filt_off is not None and filt_off.numel() != nq + 1):
-        raise L.KtupError('eval_kg_ranks: CSR offsets need len(q) + 1 entries')
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
+    _csr_offsets('eval_kg_ranks', nq, gold_off, filt_off)
     n_gold = gold_ids.numel()
     ranks = torch.empty(max(n_gold, 1), dtype=torch.int32, device=dev)
     if fused is not False and nq > 0 and n_gold > 0:
@@ -640,10 +669,8 @@ def eval_kg_ranks_transr(E, R, M, q, r, l1, head, descending, gold_off, gold_ids
     (eval_transr_entities, once per pass) + K18, the loop under the C ABI."""
     dev = _dev(_table('entity table', E)); _table('relation table', R); _table('projection table', M)
     nq = q.numel(); q = _ids('q', q, dev); r = _ids('r', r, dev, nq)
-    if filt_ids is not None and filt_ids.numel() == 0:
-        filt_off = filt_ids = None
-    if gold_off.numel() != nq + 1 or (filt_off is not None and filt_off.numel() != nq + 1):
-        raise L.KtupError('eval_kg_ranks_transr: CSR offsets need len(q) + 1 entries')
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
+    _csr_offsets('eval_kg_ranks_transr', nq, gold_off, filt_off)
     if ents is not None and (ents.shape != (E.shape[0], E.shape[1], R.shape[0]) or ents.l1 != bool(l1)):
         raise L.KtupError('prepared entity side does not match the tables / distance kind')
     ranks = torch.empty(max(gold_ids.numel(), 1), dtype=torch.int32, device=dev)
@@ -736,9 +763,7 @@ def _eval_pref(U, I, E, pref, pref_norm, rel, norm, item2ent, u, l1, gumbel_mode
         if (items.n_items, items.P, items.d) != (ni, P, d):
             raise L.KtupError('prepared item side does not match the tables')
         if gumbel_mode == GUMBEL_INPUT:
-            if uniform is None or tuple(uniform.shape) != (nq, ni, P) or uniform.dtype != torch.float32 or uniform.device != dev:
-                raise L.KtupError('uniform must be an (n_users, n_items, n_pref) fp32 device tensor')
-            uniform = uniform.contiguous()
+            uniform = _input_uniform(uniform, nq, ni, P, dev)
         else:
             uniform = None
         out = torch.empty(nq, ni, dtype=torch.float32, device=dev)
@@ -748,9 +773,7 @@ def _eval_pref(U, I, E, pref, pref_norm, rel, norm, item2ent, u, l1, gumbel_mode
         return out
     pws = pref_workspace(pref, pref_norm, rel, norm)
     if gumbel_mode == GUMBEL_INPUT:
-        if uniform is None or tuple(uniform.shape) != (nq, ni, P) or uniform.dtype != torch.float32 or uniform.device != dev:
-            raise L.KtupError('uniform must be an (n_users, n_items, n_pref) fp32 device tensor')
-        uniform = uniform.contiguous()
+        uniform = _input_uniform(uniform, nq, ni, P, dev)
     else:
         uniform = None
     if E is not None:
@@ -781,15 +804,12 @@ def eval_pref_topk(U, u, items, l1, topn, filt_off=None, filt_ids=None, with_sco
     if l1 or d not in (64, 100, 128) or not L.get_option('eval_mc'):
         # no preference-space pass for this shape: the pair kernel's arithmetic with the top-n in its epilogue (or None: per-batch calls)
         return eval_pref_topk_hard(U, u, items, l1, topn, GUMBEL_OFF, None, 0, 0, filt_off, filt_ids, with_scores)
-    if filt_ids is not None and filt_ids.numel() == 0:
-        filt_off = filt_ids = None
-    top = torch.empty(nq, topn, dtype=torch.int32, device=dev)
-    ts = torch.empty(nq, topn, dtype=torch.float32, device=dev) if with_scores else None
-    ws = _scratch(L.load().ktup_eval_pref_topk_workspace_bytes(d, P, nq, items.n_items, topn), dev)
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
     I, E = items.I, items.E
-    L.call('ktup_eval_pref_topk', _p(U), U.stride(0), _p(I), I.stride(0), _p(E), 0 if E is None else E.stride(0), _p(items.item2ent),
-           _p(items.pws), P, d, _p(u), nq, items.n_items, 0, _p(filt_off), _p(filt_ids), int(topn), _p(top), _p(ts), _p(ws), _stream(dev))
-    return (top, ts) if with_scores else top
+    args = (_p(U), U.stride(0), _p(I), I.stride(0), _p(E), 0 if E is None else E.stride(0), _p(items.item2ent), _p(items.pws), P, d, _p(u),
+            nq, items.n_items, 0, _p(filt_off), _p(filt_ids), int(topn))
+    return _topn_sweep('ktup_eval_pref_topk', args, L.load().ktup_eval_pref_topk_workspace_bytes(d, P, nq, items.n_items, topn), nq, topn,
+                       dev, with_scores, may_decline=False)
 
 
 @torch.no_grad()
@@ -805,28 +825,18 @@ def eval_pref_topk_hard(U, u, items, l1, topn, gumbel_mode, uniform=None, seed=0
     if not (0 < topn <= 16) or nq == 0 or P > 32 or d > 256:
         return None
     if gumbel_mode == GUMBEL_INPUT:
-        if uniform is None or tuple(uniform.shape) != (nq, ni, P) or uniform.dtype != torch.float32 or uniform.device != dev:
-            raise L.KtupError('uniform must be an (n_users, n_items, n_pref) fp32 device tensor')
-        uniform = uniform.contiguous()
+        uniform = _input_uniform(uniform, nq, ni, P, dev)
     elif gumbel_mode not in (GUMBEL_PHILOX, GUMBEL_OFF):
         raise L.KtupError('eval_pref_topk_hard takes GUMBEL_INPUT, GUMBEL_PHILOX or GUMBEL_OFF (the soft gate scored pair by pair)')
     else:
         uniform = None
-    if filt_ids is not None and filt_ids.numel() == 0:
-        filt_off = filt_ids = None
-    top = torch.empty(nq, topn, dtype=torch.int32, device=dev)
-    ts = torch.empty(nq, topn, dtype=torch.float32, device=dev) if with_scores else None
-    ws = _scratch(L.load().ktup_eval_pref_topk_hard_workspace_bytes(d, P, nq, ni, topn), dev)
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
     I, E = items.I, items.E
-    try:
-        L.call('ktup_eval_pref_topk_hard', _p(U), U.stride(0), _p(I), I.stride(0), _p(E), 0 if E is None else E.stride(0), _p(items.item2ent),
-               _p(items.pws), P, d, _p(u), nq, ni, int(l1), int(gumbel_mode), _p(uniform), int(seed), int(offset), _p(filt_off), _p(filt_ids),
-               int(topn), _p(top), _p(ts), _p(ws), _stream(dev))
-    except L.KtupError as e:
-        if e.code == L.ERR_UNSUPPORTED:          # a shape the sweep does not cover (a catalogue split whose filter bitmap passes the LDS):
-            return None                          # the caller keeps the per-batch calls
-        raise
-    return (top, ts) if with_scores else top
+    args = (_p(U), U.stride(0), _p(I), I.stride(0), _p(E), 0 if E is None else E.stride(0), _p(items.item2ent), _p(items.pws), P, d, _p(u),
+            nq, ni, int(l1), int(gumbel_mode), _p(uniform), int(seed), int(offset), _p(filt_off), _p(filt_ids), int(topn))
+    # (declined: a shape the sweep does not cover -- a catalogue split whose filter bitmap passes the LDS; the caller keeps the per-batch calls)
+    return _topn_sweep('ktup_eval_pref_topk_hard', args, L.load().ktup_eval_pref_topk_hard_workspace_bytes(d, P, nq, ni, topn), nq, topn,
+                       dev, with_scores)
 
 
 @torch.no_grad()
@@ -851,19 +861,11 @@ def eval_dot_topk(U, I, u, topn, filt_off=None, filt_ids=None, user_add=None, it
     user_add, item_add = _term('user_add', user_add, nq), _term('item_add', item_add, ni)
     if not (0 < topn <= 16) or nq == 0 or ni == 0 or not (0 < d <= 256):
         return None
-    if filt_ids is not None and filt_ids.numel() == 0:       # an empty id list has no storage to point at: same as no filter
-        filt_off = filt_ids = None
-    top = torch.empty(nq, topn, dtype=torch.int32, device=dev)
-    ts = torch.empty(nq, topn, dtype=torch.float32, device=dev) if with_scores else None
-    ws = _scratch(L.load().ktup_eval_dot_topk_workspace_bytes(d, nq, ni, int(topn), int(nsplit)), dev)
-    try:
-        L.call('ktup_eval_dot_topk', _p(U), U.stride(0), _p(I), I.stride(0), d, _p(u), nq, ni, _p(user_add), _p(item_add), _p(filt_off),
-               _p(filt_ids), int(topn), int(nsplit), _p(top), _p(ts), _p(ws), _stream(dev))
-    except L.KtupError as e:
-        if e.code == L.ERR_UNSUPPORTED:
-            return None
-        raise
-    return (top, ts) if with_scores else top
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
+    args = (_p(U), U.stride(0), _p(I), I.stride(0), d, _p(u), nq, ni, _p(user_add), _p(item_add), _p(filt_off), _p(filt_ids), int(topn),
+            int(nsplit))
+    return _topn_sweep('ktup_eval_dot_topk', args, L.load().ktup_eval_dot_topk_workspace_bytes(d, nq, ni, int(topn), int(nsplit)), nq, topn,
+                       dev, with_scores)
 
 
 @torch.no_grad()
@@ -885,19 +887,11 @@ def eval_cfkg_topk(U, R, rel, E, u, topn, l1, cand_ids=None, filt_off=None, filt
     nc = ne if cand_ids is None else cand_ids.numel()
     if not (0 < topn <= 16) or nq == 0 or nc == 0 or not (0 < d <= 256):
         return None
-    if filt_ids is not None and filt_ids.numel() == 0:       # an empty id list has no storage to point at: same as no filter
-        filt_off = filt_ids = None
-    top = torch.empty(nq, topn, dtype=torch.int32, device=dev)
-    ts = torch.empty(nq, topn, dtype=torch.float32, device=dev) if with_scores else None
-    ws = _scratch(L.load().ktup_eval_cfkg_topk_workspace_bytes(d, nq, nc, int(topn), int(nsplit)), dev)
-    try:
-        L.call('ktup_eval_cfkg_topk', _p(U), U.stride(0), _p(R), R.stride(0), int(rel), _p(E), E.stride(0), ne, _p(cand_ids), nc, d, _p(u), nq,
-               int(bool(l1)), _p(filt_off), _p(filt_ids), int(topn), int(nsplit), _p(top), _p(ts), _p(ws), _stream(dev))
-    except L.KtupError as e:
-        if e.code == L.ERR_UNSUPPORTED:
-            return None
-        raise
-    return (top, ts) if with_scores else top
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
+    args = (_p(U), U.stride(0), _p(R), R.stride(0), int(rel), _p(E), E.stride(0), ne, _p(cand_ids), nc, d, _p(u), nq, int(bool(l1)),
+            _p(filt_off), _p(filt_ids), int(topn), int(nsplit))
+    return _topn_sweep('ktup_eval_cfkg_topk', args, L.load().ktup_eval_cfkg_topk_workspace_bytes(d, nq, nc, int(topn), int(nsplit)), nq, topn,
+                       dev, with_scores)
 
 
 def eval_tup(U, I, pref, pref_norm, u, l1, gumbel_mode=GUMBEL_OFF, uniform=None, seed=0, offset=0, items=None):
@@ -919,8 +913,7 @@ def topk_filtered(scores, descending, topn, filt_off=None, filt_ids=None, with_s
     if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
         raise L.KtupError('scores must be a 2-D fp32 device matrix with unit inner stride')
     nq, nc = scores.shape
-    if filt_ids is not None and filt_ids.numel() == 0:       # an empty id list has no storage to point at: same as no filter
-        filt_off = filt_ids = None
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
     top = torch.empty(nq, topn, dtype=torch.int32, device=dev)
     ts = torch.empty(nq, topn, dtype=torch.float32, device=dev) if with_scores else None
     L.call('ktup_eval_topk_filtered', _p(scores), scores.stride(0), nq, nc, int(bool(descending)), _p(filt_off), _p(filt_ids),
@@ -935,8 +928,7 @@ def gold_ranks(scores, descending, gold_off, gold_ids, filt_off=None, filt_ids=N
     if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1:
         raise L.KtupError('scores must be a 2-D fp32 device matrix with unit inner stride')
     nq, nc = scores.shape
-    if filt_ids is not None and filt_ids.numel() == 0:
-        filt_off = filt_ids = None
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
     ranks = torch.empty(gold_ids.numel(), dtype=torch.int32, device=dev)
     L.call('ktup_eval_gold_ranks', _p(scores), scores.stride(0), nq, nc, int(bool(descending)), _p(filt_off), _p(filt_ids),
            _p(gold_off), _p(gold_ids), _p(ranks), _stream(dev))
@@ -952,8 +944,7 @@ def gold_rank_counts(local_scores, cand_lo, descending, gold_off, gold_ids, gold
     if local_scores.dtype != torch.float32 or local_scores.dim() != 2 or (local_scores.shape[1] and local_scores.stride(1) != 1):
         raise L.KtupError('scores must be a 2-D fp32 device matrix with unit inner stride')
     nq, nl = local_scores.shape
-    if filt_ids is not None and filt_ids.numel() == 0:
-        filt_off = filt_ids = None
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
     counts = torch.empty(gold_ids.numel(), dtype=torch.int32, device=dev)
     L.call('ktup_eval_gold_rank_counts_strided', _p(local_scores) if nl else None, local_scores.stride(0) if nl else 0, nq, nl, int(cand_lo),
            int(cand_stride), int(bool(descending)), _p(filt_off), _p(filt_ids), _p(gold_off), _p(gold_ids), _p(gold_scores.contiguous()), _p(counts),

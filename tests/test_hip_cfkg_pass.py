@@ -22,7 +22,8 @@ DEV = 'cuda'
 # (d, users, entities, n_cand, nq, topn): one and several user blocks with ragged last waves, fewer candidates than topn, candidate
 # counts that are no multiple of the 16-candidate tile or of a stage, d = 50 on the element-wise path, d = 256 at the widest geometry
 SHAPES = [(36, 70, 53, 53, 9, 10), (64, 300, 177, 177, 65, 16), (100, 90, 16, 16, 1, 3), (100, 70, 9, 5, 63, 10),
-          (100, 500, 1000, 1000, 129, 1), (256, 80, 211, 150, 37, 10), (50, 40, 60, 60, 20, 10)]
+          (100, 500, 1000, 1000, 129, 1), (256, 80, 211, 150, 37, 10), (50, 40, 60, 60, 20, 10), (20, 40, 53, 40, 9, 10),
+          (128, 40, 70, 70, 17, 10), (192, 40, 70, 50, 17, 16)]
 NR = 4
 _CASES = {}
 

@@ -74,7 +74,8 @@ def filters_all_but_two(rng, nq, ni):
 # last one short) -- with topn 16 the merge kernel's full 512 keys
 MANY_SPLITS = [(12, 70, 531, 70, 16), (12, 70, 531, 70, 3), (12, 70, 499, 70, 16)]
 SHAPES = [(64, 300, 177, 65, 16), (100, 70, 5, 63, 10), (37, 90, 33, 1, 3), (50, 500, 1000, 129, 1), (20, 64, 45, 33, 10),
-          (256, 40, 130, 17, 10), (8, 50, 40000, 33, 10), (64, 6040, 3240, 6040, 10)]
+          (256, 40, 130, 17, 10), (8, 50, 40000, 33, 10), (64, 6040, 3240, 6040, 10), (128, 40, 70, 17, 10), (192, 40, 70, 17, 16),
+          (131, 40, 37, 5, 3)]
 _CASES = {}
 
 

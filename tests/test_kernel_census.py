@@ -1,5 +1,5 @@
 """The kernel census tool (tools/kernel_census.py) on canned symbol lists and canned rocprofv3 CSVs: the matching of traced kernel names
-to compiled instantiations, without a GPU -- and the symbol listing on the built library, which holds 917 instantiations at this commit.
+to compiled instantiations, without a GPU -- and the symbol listing on the built library, which holds 1115 instantiations at this commit.
 
 The census itself (the GPU suite module by module under `rocprofv3 --kernel-trace --stats -M --output-format csv -d <dir>/<module> --
 python -m pytest -m gpu tests/<module>.py`, then `python tools/kernel_census.py join --symbols build --modules ... -o

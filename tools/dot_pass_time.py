@@ -98,7 +98,7 @@ def profile(out):
     rows = []
     for path in glob.glob(os.path.join(tmp, '**', '*kernel_trace.csv'), recursive=True):
         rows += list(csv.DictReader(open(path)))
-    for name in ('dot_pass_kernel', 'topk_merge_kernel', 'dot_filter_bits_kernel', 'dot_filter_zero_kernel'):
+    for name in ('dot_pass_kernel', 'topk_merge_kernel', 'filter_bits_kernel', 'filter_zero_kernel'):
         mine = [r for r in rows if name in r.get('Kernel_Name', '')]
         if not mine:
             out.append('%s: not in the trace' % name)
