@@ -210,7 +210,10 @@ int ktup_loss_margin_bwd(const float* pos, const float* neg, int64_t n, float ma
  * norm : sum over rows T[ids[i]] of max(|x|^2 - 1, 0);  orth: sum over rows of (Nrm[r].Rel[r])^2 / |Rel[r]|^2.
  * ids == NULL means rows 0..n-1 (whole table); otherwise the gather the reference does with a second
  * nn.Embedding lookup (item_recommendation.py:177-180, knowledge_representation.py:197-204) is fused.
- * Backward accumulates into table-shaped gradients (same pitch as the table).                            */
+ * Backward accumulates into table-shaped gradients (same pitch as the table).
+ * Width limit: a row is at most 256 chunks -- d <= 1024 when d % 4 == 0, every pitch is a multiple of 4 floats and every table
+ * and gradient pointer of the call is 16-byte aligned (16-byte chunks), d <= 256 otherwise (4-byte chunks).  A wider row with
+ * n > 0 is KTUP_ERR_UNSUPPORTED for all six entry points (_fused below included): nothing is launched and nothing written.  */
 int ktup_reg_norm_fwd(const float* T, int64_t ld, int d, const int64_t* ids, int64_t n, float* loss, void* stream);
 int ktup_reg_norm_bwd(const float* T, int64_t ld, int d, const int64_t* ids, int64_t n, const float* gloss,
                       float* gT, void* stream);

@@ -125,9 +125,11 @@ __global__ __launch_bounds__(256) void row_reduce_kernel(Op op, int nch, int64_t
 
 template <typename Op>
 int launch_rows_reduce(const Op& op, int d, bool vec4, int64_t n, float* out, hipStream_t st, const char* name, bool zero_first = true) {
+  const int nch = vec4 ? d / 4 : d;
+  // a width no rung covers is refused before anything is written (not even the zero of a value that is overwritten)
+  if (n > 0 && nch > 256) return set_error(KTUP_ERR_UNSUPPORTED, "%s: embedding_size %d too large for the row kernels", name, d);
   if (zero_first && hipMemsetAsync(out, 0, sizeof(float), st) != hipSuccess) return check_launch(name);
   if (n == 0) return KTUP_OK;
-  const int nch = vec4 ? d / 4 : d;
 #define KTUP_L(V, G, CPL)                                                                                   \
   {                                                                                                         \
     const int serial = opt_deterministic() != 0;                                                            \

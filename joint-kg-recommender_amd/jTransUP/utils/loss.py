@@ -20,12 +20,15 @@ class marginLoss(nn.Module):
 
 
 def orthogonalLoss(rel_embeddings, norm_embeddings, ids=None):
-    """utils/loss.py:18-19."""
+    """utils/loss.py:18-19.  Width limit of the row kernels (include/ktup_hip.h, K10): embedding_size <= 1024 when it is a multiple
+    of 4 and the tables and their gradients are 16-byte aligned with a pitch that is a multiple of 4 floats, <= 256 otherwise;
+    a wider table raises (KTUP_ERR_UNSUPPORTED), nothing is computed."""
     return ops.orthogonal_loss(rel_embeddings, norm_embeddings, ids)
 
 
 def normLoss(embeddings, dim=1, ids=None):
-    """utils/loss.py:21-23 (only dim=1, the one the reference ever uses)."""
+    """utils/loss.py:21-23 (only dim=1, the one the reference ever uses).  Width limit as for orthogonalLoss: embedding_size <= 1024
+    on 16-byte aligned tables of a width and pitch that are multiples of 4, <= 256 otherwise; wider raises (KTUP_ERR_UNSUPPORTED)."""
     if dim != 1:
         raise NotImplementedError('normLoss: only dim=1 is used by the reference drivers')
     return ops.norm_loss(embeddings, ids)

@@ -183,24 +183,41 @@ def test_ragged_tails_vs_oracle(n):
     close(ops().score_bprmf(D['U'], D['I'], u.to(DEV), i.to(DEV)), O.score_bprmf(W['U'], W['I'], u, i))
 
 
-@pytest.mark.parametrize('d', [50, 7, 130, 256])
+@pytest.mark.parametrize('d', [50, 7, 130, 256, 20, 100, 260, 516])
 def test_odd_and_unaligned_tables_vs_oracle(d):
-    """d % 4 != 0 and tables that are views at a 4-byte offset take the 4-byte-lane path of K1-K3."""
+    """d % 4 != 0 and tables that are views at a 4-byte offset take the 4-byte-lane path of K1-K3.  The last four widths are the
+    rungs of ktup_rows.h the others miss, forward AND backward against the oracle evaluated in fp64: d = 20 and 100 at the offset
+    only (float G32 and float G64 with two chunks per lane), d = 260 and 516 aligned only (float4 G64 with two and four chunks
+    per lane; at the offset they would be more than 256 4-byte chunks, which the row kernels refuse).  ops sends every backward to
+    the *_bwd_ws entries; at n = 300 (below the option seg_bwd_min, 8192) those forward to ktup_score_{bprmf,transe,transh}_bwd,
+    the row kernels with float atomics, so that is the entry each backward case reaches."""
     gen = torch.Generator().manual_seed(d)
     n = 300
     E = O.make_table(40, d, gen); R = O.make_table(9, d, gen); N = O.make_table(9, d, gen)
     h = torch.randint(0, 40, (n,), generator=gen); t = torch.randint(0, 40, (n,), generator=gen); r = torch.randint(0, 9, (n,), generator=gen)
-    for shift in (0, 1):
+    new_rung = d in (20, 100, 260, 516)
+    gs = torch.randn(n, generator=gen)
+    for shift in ((1,) if d in (20, 100) else (0,) if d > 256 else (0, 1)):
         def place(x):
             buf = torch.zeros(x.numel() + 4, device=DEV)
             v = buf[shift:shift + x.numel()].view(x.shape)
             v.copy_(x)
-            return v
+            return v.requires_grad_(new_rung)
         Ed, Rd, Nd = place(E), place(R), place(N)
-        for l1 in (False, True):
-            close(ops().score_transe(Ed, Rd, h.to(DEV), t.to(DEV), r.to(DEV), l1), O.score_transe(E, R, h, t, r, l1))
-            close(ops().score_transh(Ed, Rd, Nd, h.to(DEV), t.to(DEV), r.to(DEV), l1), O.score_transh(E, R, N, h, t, r, l1))
-        close(ops().score_bprmf(Ed, Ed, h.to(DEV), t.to(DEV)), O.score_bprmf(E, E, h, t))
+        assert Ed.data_ptr() % 16 == 4 * shift
+        E64, R64, N64 = (x.double().requires_grad_(new_rung) for x in (E, R, N))
+        pairs = [(ops().score_transe(Ed, Rd, h.to(DEV), t.to(DEV), r.to(DEV), l1), O.score_transe(E64, R64, h, t, r, l1)) for l1 in (False, True)]
+        pairs += [(ops().score_transh(Ed, Rd, Nd, h.to(DEV), t.to(DEV), r.to(DEV), l1), O.score_transh(E64, R64, N64, h, t, r, l1)) for l1 in (False, True)]
+        pairs.append((ops().score_bprmf(Ed, Ed, h.to(DEV), t.to(DEV)), O.score_bprmf(E64, E64, h, t)))
+        for got, want in pairs:
+            close(got, want.float())
+            if new_rung:
+                for x in (Ed, Rd, Nd, E64, R64, N64):
+                    x.grad = None
+                got.backward(gs.to(DEV)); want.backward(gs.double())
+                for gd, g64 in ((Ed, E64), (Rd, R64), (Nd, N64)):
+                    if g64.grad is not None:
+                        close(gd.grad, g64.grad.float(), atol=GAT)
 
 
 def _l1_knife_edge(W, i2e, u, i, uni, ktup, eps=1e-7):
