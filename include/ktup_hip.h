@@ -801,6 +801,30 @@ int ktup_eval_kg_ranks_transd(const float* E, int64_t lde, const float* Ep, int6
                               const int64_t* filt_off, const int32_t* filt_ids, const int64_t* gold_off,
                               const int32_t* gold_ids, int32_t* ranks, int64_t chunk, void* ws, void* stream);
 
+/* ------------------------------------------------------------------ the same pass WITHOUT the score matrix
+ * knowledge_representation.py:93-146 + utils/misc.py:125-146 (the filtered rank walk) over transD.py:78-134's scores, as
+ * ktup_eval_kg_ranks_fused does it for TransE / TransH: all nq keys in one go, no chunk, no side stream;
+ *     ranks[g] = #{c : key(c) < key(g)} - #{c in filter(q) U gold(q), c != g : key(c) < key(g)},  key = (score image << 32 | id),
+ * counted where the scores are made.  The scores are those of ktup_eval_transd_scores bit for bit (one copy of the device code), so
+ * the ranks are the INTEGERS of ktup_eval_kg_ranks_transd; there is no fp64 referee for TransD.  Arguments as
+ * ktup_eval_kg_ranks_transd (absolute CSR offsets of nq + 1 entries; ranks[g] the filtered 0-based rank, -1 for a gold that is itself
+ * filtered) plus n_filt / n_gold (entries of the two id arrays) and max_golds (the longest gold list), as ktup_eval_kg_ranks_fused.
+ * Squared L2 at d in {20, 36, 64, 100, 128} with 16-byte aligned candidate rows of a pitch % 4 == 0 takes the matrix-core sweep
+ * (option "eval_mc" = 0: not); L1, every other width and every other layout take the pair kernel's list and COUNT forms.
+ * ktup_eval_kg_ranks_transd_fused_supported: 1 if the pass takes this width (round4(d) <= 640: the pair kernel's LDS stage; wider
+ * rows are declined by the chunked route as well), else 0.  The call itself returns KTUP_ERR_UNSUPPORTED before any HIP call for
+ * such a width, for more than 65535 x 64 keys and for 2^31 or more candidates: the caller keeps ktup_eval_kg_ranks_transd.
+ * ws: ktup_eval_kg_ranks_transd_fused_workspace_bytes(...) bytes, 16-byte aligned: the key rows, one float per gold, filtered id
+ * and candidate, one int per gold -- nothing in nq x n_cand.                                                                    */
+int ktup_eval_kg_ranks_transd_fused_supported(int d, int l1, int64_t max_golds);
+size_t ktup_eval_kg_ranks_transd_fused_workspace_bytes(int d, int64_t nq, int64_t n_gold, int64_t n_filt, int64_t n_cand);
+int ktup_eval_kg_ranks_transd_fused(const float* E, int64_t lde, const float* Ep, int64_t ldep, const float* R, int64_t ldr,
+                                    const float* Rp, int64_t ldrp, int d, const float* C, int64_t ldc, int64_t n_cand,
+                                    const int64_t* q, const int64_t* r, int64_t nq, int l1, int head, int descending,
+                                    const int64_t* filt_off, const int32_t* filt_ids, int64_t n_filt, const int64_t* gold_off,
+                                    const int32_t* gold_ids, int64_t n_gold, int64_t max_golds, int32_t* ranks, void* ws,
+                                    void* stream);
+
 /* =================================================================== inner-product evaluation pass (csrc/ktup_dot_pass.hip)
  * The whole-pass evaluation of the inner-product recommenders (BPRMF bprmf.py:51-54, FM fm.py:69-80, CKE CKE.py:142-153 and coFM
  * cofm.py:127-141): all-item scores AND the filtered top-n of every user in one sweep that never writes the (users x items)

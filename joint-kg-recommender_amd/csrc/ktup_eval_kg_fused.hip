@@ -802,6 +802,18 @@ bool wtab_on(int model, int64_t n_cand, int64_t n_rel) {
 }
 
 }  // namespace
+
+// the finalize step for a pass that made its own counts and list scores (ktup_transd_eval.hip): no window, the keys of the scores decide
+int kg_rank_finalize(const int64_t* gold_off, const int32_t* gold_ids, const float* gscore, const int64_t* filt_off, const int32_t* filt_ids,
+                     float* fscore, int32_t* counts, int32_t* ranks, int64_t nq, int64_t n_cand, int64_t n_gold, int descending,
+                     hipStream_t st, const char* name) {
+  FArgs a{};
+  a.nq = nq; a.n_cand = n_cand; a.descending = descending; a.gold_off = gold_off; a.gold_ids = gold_ids; a.gscore = gscore;
+  a.filt_off = filt_off; a.filt_ids = filt_ids; a.fscore = fscore; a.counts = counts; a.ranks = ranks; a.ktol = nullptr;
+  hipLaunchKernelGGL(kg_rank_finalize_kernel, dim3(fin_blocks(nq)), dim3(256), 0, st, a, n_gold);
+  return check_launch(name);
+}
+
 }  // namespace ktup
 
 // the matrix-core sweep applies; everything else TransE / TransH takes the VALU count route (ktup_eval.hip kg_valu_counts)

@@ -88,6 +88,11 @@ int kg_valu_counts(int model, const float* QW, int d, const float* C, int64_t ld
                    const int64_t* gold_off, const int32_t* gold_ids, const int64_t* filt_off, const int32_t* filt_ids, float* gscore,
                    float* fscore, int32_t* counts, const int64_t* rel, const float* Nrm, int64_t ldn, int64_t n_rel, float* wtab, int64_t ldw,
                    hipStream_t st, const char* name);
+// ktup_eval_kg_fused.hip: the last step of a count pass -- ranks[g] = counts[g] - (filtered ids and other golds of the key ordered
+// before gold g, from the list scores gscore / fscore by their 64-bit keys), -1 for a gold that is itself filtered; counts <- 0
+int kg_rank_finalize(const int64_t* gold_off, const int32_t* gold_ids, const float* gscore, const int64_t* filt_off, const int32_t* filt_ids,
+                     float* fscore, int32_t* counts, int32_t* ranks, int64_t nq, int64_t n_cand, int64_t n_gold, int descending,
+                     hipStream_t st, const char* name);
 int launch_topk_merge(const uint64_t* part, int64_t nq, int nsplit, int topn, int32_t* top_ids, float* top_scores, hipStream_t st, const char* name);
 int eval_pass_pspace(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, const float* I, int64_t ldi, const float* E, int64_t lde,
                      const int32_t* item2ent, int64_t n_items, const float* pref_ws,

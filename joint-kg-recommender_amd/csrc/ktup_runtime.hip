@@ -61,6 +61,8 @@ Option g_opts[] = {
                                                                             // per id, buffer loads at 32-bit offsets, per-tile fall-back for rows past 4 GB: ktup_score_pref_mc.hip)
     {"fwd_split_pack", "KTUP_FWD_SPLIT_PACK", {env_int("KTUP_FWD_SPLIT_PACK", 1)}},   // 0: the split stage 2 (fwd_split) issues its six products as six MFMAs per tile and table for every P (1: at P <= 20
                                                                             // packed into four, at P <= 16 three, by ktup_split_plan.h)
+    {"transd_fused", "KTUP_TRANSD_FUSED", {env_int("KTUP_TRANSD_FUSED", 1)}},         // 0: the TransD link-prediction pass keeps the chunked score-matrix route; read by the callers
+                                                                            // (ktup_get_option; ops.eval_kg_ranks_transd), who otherwise take ktup_eval_kg_ranks_transd_fused: the same ranks
 };
 Option* find(const char* name) {
   for (auto& o : g_opts)

@@ -583,11 +583,20 @@ def eval_transd(E, R, Ep, Rp, q, r, l1, head, candidates=None):
     return out
 
 
+# l1 -> whether the TransD pass without the score matrix is the default for that distance: only where its median gain over the chunked
+# route exceeded the spread in both runs of tools/transd_pass_time.py (profiles/transd_pass_times.txt)
+TRANSD_FUSED_DEFAULT = {False: True, True: True}
+TRANSD_PASS_ROUTE = [None]       # the route the last eval_kg_ranks_transd call took (the KG driver logs it)
+
+
 @torch.no_grad()
 def eval_kg_ranks_transd(E, R, Ep, Rp, q, r, l1, head, descending, gold_off, gold_ids, filt_off=None, filt_ids=None, candidates=None,
-                         chunk=512):
-    """eval_kg_ranks for TransD (ktup_eval_kg_ranks_transd): the score matrix of `chunk` keys at a time + K18, the loop under the C ABI.
-    -> int32 [gold_off[-1]]; -1 = a gold id that is itself filtered."""
+                         chunk=512, fused=None):
+    """eval_kg_ranks for TransD -> int32 [gold_off[-1]]; -1 = a gold id that is itself filtered.  Two routes with the same integers:
+    the pass without the score matrix (ktup_eval_kg_ranks_transd_fused: all keys in one go, ranks from counts formed where the scores
+    are made) and the chunked one (ktup_eval_kg_ranks_transd: the score matrix of `chunk` keys at a time + K18, the loop under the C
+    ABI).  fused=False: chunked; True: the pass wherever it covers the shape; None: the pass where it is the default
+    (TRANSD_FUSED_DEFAULT per distance, library option transd_fused / KTUP_TRANSD_FUSED=0: chunked)."""
     nq = q.numel()
     filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
     _csr_offsets('eval_kg_ranks_transd', nq, gold_off, filt_off)      # (a shape check: before anything else)
@@ -595,8 +604,27 @@ def eval_kg_ranks_transd(E, R, Ep, Rp, q, r, l1, head, descending, gold_off, gol
     _table('entity projection table', Ep); _table('relation projection table', Rp)
     C = E if candidates is None else _table('candidate table', candidates)
     q = _ids('q', q, dev); r = _ids('r', r, dev, nq)
-    ranks = torch.empty(max(gold_ids.numel(), 1), dtype=torch.int32, device=dev)
+    n_gold = gold_ids.numel()
+    ranks = torch.empty(max(n_gold, 1), dtype=torch.int32, device=dev)
+    if fused is None:
+        fused = TRANSD_FUSED_DEFAULT[bool(l1)] and L.get_option('transd_fused') != 0
+    if fused and nq > 0 and n_gold > 0:
+        mg = _max_golds(gold_off)
+        lib = L.load()
+        if lib.ktup_eval_kg_ranks_transd_fused_supported(E.shape[1], int(bool(l1)), mg):
+            n_filt = 0 if filt_ids is None else filt_ids.numel()
+            fws = _scratch(lib.ktup_eval_kg_ranks_transd_fused_workspace_bytes(E.shape[1], nq, n_gold, n_filt, C.shape[0]), dev)
+            try:
+                L.call('ktup_eval_kg_ranks_transd_fused', _p(E), E.stride(0), _p(Ep), Ep.stride(0), _p(R), R.stride(0), _p(Rp), Rp.stride(0),
+                       E.shape[1], _p(C), C.stride(0), C.shape[0], _p(q), _p(r), nq, int(bool(l1)), int(head), int(bool(descending)),
+                       _p(filt_off), _p(filt_ids), n_filt, _p(gold_off), _p(gold_ids), n_gold, mg, _p(ranks), _p(fws), _stream(dev))
+                TRANSD_PASS_ROUTE[0] = 'no score matrix (ktup_eval_kg_ranks_transd_fused)'
+                return ranks
+            except L.KtupError as e:
+                if e.code != L.ERR_UNSUPPORTED:        # sizes the pass declines (see include/ktup_hip.h): the chunked route below
+                    raise
     chunk = max(1, min(int(chunk), max(nq, 1)))
+    TRANSD_PASS_ROUTE[0] = 'chunked score matrix (ktup_eval_kg_ranks_transd)'
     ws = _scratch(L.load().ktup_eval_kg_ranks_transd_workspace_bytes(E.shape[1], C.shape[0], chunk), dev)
     L.call('ktup_eval_kg_ranks_transd', _p(E), E.stride(0), _p(Ep), Ep.stride(0), _p(R), R.stride(0), _p(Rp), Rp.stride(0), E.shape[1],
            _p(C), C.stride(0), C.shape[0], _p(q), _p(r), nq, int(l1), int(head), int(bool(descending)), _p(filt_off), _p(filt_ids),

@@ -134,6 +134,10 @@ def train_loop(FLAGS, model, trainer, train_dataset, eval_datasets, entity_total
         logger.info('TransD training step: {}; {} steps were graph replays; device-fed: {}.'.format(
             'one launch (ktup_train_transd_step)' if stepper.transd_step else 'multi-launch route',
             stepper.replays['kg'] + stepper.fed_replays['kg'], 'yes' if feed is not None and stepper.can_feed('kg') else 'no'))
+    if FLAGS.model_type == 'transd':
+        from jTransUP.hip import ops
+        if ops.TRANSD_PASS_ROUTE[0] is not None:
+            logger.info('TransD link-prediction pass: {} (KTUP_TRANSD_FUSED=0 keeps the chunked route).'.format(ops.TRANSD_PASS_ROUTE[0]))
     trainer.save(trainer.checkpoint_path + '_final')      # knowledge_representation.py:219
 
 

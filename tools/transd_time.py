@@ -1,7 +1,7 @@
 """TransD timings on one MI355X, one process:
 
   * the whole link-prediction pass at the shape of tools/kg_eval_pass.py (20,480 keys x 14,709 entities, 20 relations, d = 100,
-    1-3 gold entities and 20 filtered entities per key), squared L2 and L1: ops.eval_kg_ranks_transd against TransH through the same
+    1-3 gold entities and 20 filtered entities per key), squared L2 and L1: ops.eval_kg_ranks_transd(fused=False) against TransH through the same
     kind of route, ops.eval_kg_ranks(..., fused=False) (score matrix per 512-key chunk + the rank kernel), on tables of the same shape;
   * the B = 512 KGStepper step for TransD against TransR's multi-launch step (same launch-count class), d = 100: both as eager
     launches, TransD also replayed from its captured graph (see step_figures for why TransR is not).
@@ -56,7 +56,7 @@ def pass_figures(repeats, lines):
     f_ids = torch.from_numpy(rng.randint(0, ne, 20 * nq).astype(np.int32)).to(dev)
     for l1 in (False, True):
         th = median_ms(lambda: ops.eval_kg_ranks(E, R, Rp, q, r, l1, False, False, g_off, g_ids, f_off, f_ids, chunk=512, fused=False), repeats)
-        td = median_ms(lambda: ops.eval_kg_ranks_transd(E, R, Ep, Rp, q, r, l1, False, False, g_off, g_ids, f_off, f_ids, chunk=512), repeats)
+        td = median_ms(lambda: ops.eval_kg_ranks_transd(E, R, Ep, Rp, q, r, l1, False, False, g_off, g_ids, f_off, f_ids, chunk=512, fused=False), repeats)
         kind = 'L1' if l1 else 'L2'
         lines.append('pass %s  %d keys x %d entities d=%d chunk 512: TransH (eval_kg_ranks fused=False) %.3f ms [min %.3f max %.3f]   '
                      'TransD (eval_kg_ranks_transd) %.3f ms [min %.3f max %.3f]   ratio TransD / TransH %.3f   (median of %d)'
