@@ -825,6 +825,39 @@ int ktup_eval_kg_ranks_transd_fused(const float* E, int64_t lde, const float* Ep
                                     const int32_t* gold_ids, int64_t n_gold, int64_t max_golds, int32_t* ranks, void* ws,
                                     void* stream);
 
+/* =================================================================== TransR: the link-prediction pass WITHOUT the score matrix
+ * knowledge_representation.py:93-146 + utils/misc.py:125-146 (the filtered rank walk) over transR.py:80-128's scores, as
+ * ktup_eval_kg_ranks_transd_fused does it for TransD: all nq keys in one go, no chunk, no side stream;
+ *     ranks[g] = #{c : key(c) < key(g)} - #{c in filter(q) U gold(q), c != g : key(c) < key(g)},  key = (score image << 32 | id),
+ * counted where the scores are made.  The scores are those of ktup_eval_transr_scores bit for bit (one copy of the device code), so
+ * the ranks are the INTEGERS of ktup_eval_kg_ranks_transr; there is no fp64 referee for TransR.  Arguments as
+ * ktup_eval_kg_ranks_transr (absolute CSR offsets of nq + 1 entries; ranks[g] the filtered 0-based rank, -1 for a gold that is itself
+ * filtered; the candidates are the entity table itself) plus n_filt / n_gold (entries of the two id arrays) and max_golds (the longest
+ * gold list).
+ * ents_ws: what ktup_eval_transr_prepare left for the SAME tables, l1 and "eval_mc" setting.  REQUIRED: NULL returns
+ * KTUP_ERR_INVALID_ARG before any HIP call (the pass has no room to prepare the entity side per call).
+ * Squared L2 at d in {64, 100, 128} with 16-byte aligned entity rows of a pitch % 4 == 0 (ents_ws = |M_r e|^2 per relation and
+ * entity) takes the matrix-core count sweep: the folded query M_r^T c against the UNPROJECTED entity table plus one table look-up per
+ * (key, candidate).  L1, every other width, every other layout and option "eval_mc" = 0 (ents_ws = the projected table) take the pair
+ * kernel's list and COUNT forms with the keys bucketed by relation.
+ * ktup_eval_kg_ranks_transr_fused_supported: 1 if the pass takes this width (round4(d) <= 256: the widest row
+ * ktup_eval_transr_prepare projects, inside the pair kernels' LDS stage), else 0.  The call itself returns KTUP_ERR_UNSUPPORTED
+ * before any HIP call for such a width, for more than 65535 x 64 keys, for 2^31 or more entities, for more than 16384 relations
+ * (the bucket kernel's LDS counters) and -- on the matrix-core route -- for a norm table of (n_rel x n_ent + 1024) x 4 bytes >= 2^31
+ * or a band (one eighth, rounded up to 64-row tiles, plus one tile) of the entity table of 2^31 bytes or more: both are read through
+ * 32-bit buffer ranges.  The caller then keeps ktup_eval_kg_ranks_transr.
+ * ws: ktup_eval_kg_ranks_transr_fused_workspace_bytes(...) bytes, 16-byte aligned: the key rows, three words per key, one float per
+ * gold and filtered id, one int per gold and relation -- nothing in nq x n_ent.
+ * The entry itself issues no hipMemsetAsync (counts are cleared by an init kernel).  ktup_eval_transr_prepare still goes through the
+ * bucketed kernels' memset, so a TransR pass (prepare + ranks) is never captured into a graph.                                  */
+int ktup_eval_kg_ranks_transr_fused_supported(int d, int l1, int64_t max_golds);
+size_t ktup_eval_kg_ranks_transr_fused_workspace_bytes(int d, int64_t nq, int64_t n_gold, int64_t n_filt, int64_t n_ent, int n_rel);
+int ktup_eval_kg_ranks_transr_fused(const float* E, int64_t lde, const float* R, int64_t ldr, const float* M, int64_t ldm, int d,
+                                    int64_t n_ent, int n_rel, const float* ents_ws, const int64_t* q, const int64_t* r, int64_t nq,
+                                    int l1, int head, int descending, const int64_t* filt_off, const int32_t* filt_ids, int64_t n_filt,
+                                    const int64_t* gold_off, const int32_t* gold_ids, int64_t n_gold, int64_t max_golds,
+                                    int32_t* ranks, void* ws, void* stream);
+
 /* =================================================================== inner-product evaluation pass (csrc/ktup_dot_pass.hip)
  * The whole-pass evaluation of the inner-product recommenders (BPRMF bprmf.py:51-54, FM fm.py:69-80, CKE CKE.py:142-153 and coFM
  * cofm.py:127-141): all-item scores AND the filtered top-n of every user in one sweep that never writes the (users x items)

@@ -1060,7 +1060,8 @@ __global__ __launch_bounds__(LIST_NW * 64) void pairs_list_kernel(PairsArgs a) {
       const bool on = e < ng + nf;
       const int32_t cid = !on ? 0 : (e < ng ? a.gold_ids[g0 + e] : a.filt_ids[f0 + (e - ng)]);
       const bool valid = on && cid >= 0 && cid < a.n_cand;
-      const float* row = a.C0 + (int64_t)(valid ? cid : 0) * a.ldc0;
+      // (TransR's pass: the candidates are the key's relation's projected table, as grid.z picks it in the COUNT form)
+      const float* row = a.C0 + (a.qperm ? a.rel[key] * a.rel_stride : 0) + (int64_t)(valid ? cid : 0) * a.ldc0;
       float acc[1], stab[1] = {0.f};
       if constexpr (MODE == 3) stab[0] = a.wtab[a.rel[key] * a.ldw + (valid ? cid : 0)];
       if (a.cvec) pair_group_scores<MODE, L1, 1>(RowCand<true>{row, a.d}, nch4, qa, qn, q1p, acc, stab);
@@ -1110,7 +1111,10 @@ int launch_pairs_count(const PairsArgs& a, hipStream_t st, const char* name) {
     hipLaunchKernelGGL(pairs_wtab_kernel, dim3((unsigned)((a.n_cand + CT - 1) / CT)), dim3(256), tile, st, a);
   }
   hipLaunchKernelGGL((pairs_list_kernel<MODE, L1>), dim3(grid_for((a.nq + LIST_NW - 1) / LIST_NW, 8192)), dim3(LIST_NW * 64), 0, st, a);
-  const dim3 grid = pairs_grid(a.n_cand, a.nq, PairsWG<MODE>::NWV, 2048, 1536);
+  // keys bucketed by relation (TransR): grid.z = relation, and grid.y splits the keys of ONE bucket -- sized for an average one
+  const int nrel = a.qperm ? a.n_rel : 1;
+  dim3 grid = pairs_grid(a.n_cand, (a.nq + nrel - 1) / nrel, PairsWG<MODE>::NWV, 2048, 1536);
+  grid.z = (unsigned)nrel;
   if (tile > 64 * 1024) (void)hipFuncSetAttribute((const void*)pairs_kernel<MODE, L1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile);
   hipLaunchKernelGGL((pairs_kernel<MODE, L1, true>), grid, dim3(PairsWG<MODE>::NT), tile, st, a);
   return check_launch(name);
@@ -1178,6 +1182,33 @@ int ktup::kg_valu_counts(int model, const float* QW, int d, const float* C, int6
   return l1 ? launch_pairs_count<0, true>(a, st, name) : launch_pairs_count<0, false>(a, st, name);
 }
 
+// TransR's pass without the score matrix (ktup_eval_kg_fused.hip), pair form: the keys bucketed by relation, then the list and COUNT
+// forms over the projected table PE[rho][e][round4(d)] of ktup_eval_transr_prepare.  QW: kg_query_prep's rows (model 2); counts must be
+// zero on entry; rel_off [n_rel + 1] and qperm [nq] are scratch.
+// KNOWN LIMIT: rel_bucket_kernel is ONE 256-thread workgroup (written for the chunked route's 512 keys); here it sorts all keys of the
+// pass, so its time grows linearly with nq on one CU.  Not timed by itself; the 20,480-key passes of profiles/transr_pass_times.txt
+// include it.
+int ktup::transr_pair_counts(const float* QW, int d, const float* PE, int64_t n_ent, int n_rel, int64_t nq, int l1, int descending,
+                             const int64_t* gold_off, const int32_t* gold_ids, const int64_t* filt_off, const int32_t* filt_ids, float* gscore,
+                             float* fscore, int32_t* counts, const int64_t* rel, int32_t* rel_off, int32_t* qperm, hipStream_t st,
+                             const char* name) {
+  hipLaunchKernelGGL(rel_bucket_kernel, dim3(1), dim3(256), (size_t)n_rel * 4, st, rel, nq, n_rel, rel_off, qperm);
+  if (int e = check_launch(name)) return e;
+  PairsArgs a{};
+  a.C0 = PE; a.ldc0 = round4(d); a.QW = QW; a.n_cand = n_ent; a.nq = nq; a.d = d; a.dq = round4(d); a.l1 = l1;
+  a.cvec = 1; a.qperm = qperm; a.rel_off = rel_off; a.rel_stride = n_ent * (int64_t)round4(d); a.rel = rel; a.n_rel = n_rel;
+  a.gold_off = gold_off; a.gold_ids = gold_ids; a.filt_off = filt_off; a.filt_ids = filt_ids; a.gscore = gscore; a.fscore = fscore;
+  a.counts = counts; a.descending = descending;
+  return l1 ? launch_pairs_count<0, true>(a, st, name) : launch_pairs_count<0, false>(a, st, name);
+}
+
+// the query fold of the squared-L2 matrix-core route, for the pass: slot 0 <- M_r^T c, qcc <- |c|^2, qrel <- the relation id
+int ktup::transr_query_fold(float* QW, int dq, const float* M, int64_t ldm, int d, const int64_t* r, int64_t nq, float* qcc, int32_t* qrel,
+                            hipStream_t st, const char* name) {
+  hipLaunchKernelGGL(transr_query_fold_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, QW, dq, M, ldm, d, r, nq, qcc, qrel);
+  return check_launch(name);
+}
+
 extern "C" size_t ktup_eval_kg_workspace_bytes(int d, int64_t nq) { return (size_t)nq * 3 * round4(d) * sizeof(float); }
 
 extern "C" size_t ktup_eval_pref_workspace_bytes(int d, int n_pref, int64_t nq, int64_t n_items) {
@@ -1232,6 +1263,10 @@ namespace {
 bool transr_mc_route(int d, int l1, const float* E, int64_t lde) {
   return !l1 && (d == 64 || d == 100 || d == 128) && aligned16(E) && lde % 4 == 0 && ktup::opt_eval_mc();
 }
+}  // namespace
+// (the pass asks the same question, so that it reads `ents_ws` as ktup_eval_transr_prepare wrote it)
+bool ktup::transr_pass_mc_route(int d, int l1, const float* E, int64_t lde) { return transr_mc_route(d, l1, E, lde); }
+namespace {
 
 // norms[n_rel][n_ent] at the head of `region` (`avail` bytes); the rest of the region is this route's scratch.
 // Returns KTUP_OK / an error, or 1 when the region is too small or the shape has no matrix-core kernel.

@@ -38,12 +38,19 @@
 // counts stay consistent.
 // The sweep covers squared L2 at d in {20, 36, 64, 100, 128}; L1 and every other width take the pair kernels' COUNT form
 // (ktup_eval.hip kg_valu_counts) behind the same entry point, with this file's finalize step.
+// TransR (ktup_eval_kg_ranks_transr_fused, at the end of this file) is mode 3 of the same sweep at d in {64, 100, 128}: the query is
+// folded once (c' = M_r^T c), the product runs against the UNPROJECTED entity table and |M_r e|^2 is looked up per (key, candidate) in
+// the (relations x entities) table of ktup_eval_transr_prepare, as mode 2 looks up w.e.  No window and no fp64 referee there: the
+// scores are the bits of the chunked route's (ktup_kg_mc_tile.h holds the one copy of the product and the epilogue), so the keys of
+// the scores give the chunked route's integers.  L1 and the other shapes: the pair kernels over the projected table, keys bucketed by
+// relation (ktup_eval.hip transr_pair_counts).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <type_traits>
 
 #include "ktup_common.h"
+#include "ktup_kg_mc_tile.h"
 #include "ktup_lane_swap.h"
 #include "ktup_pref_geom.h"
 #include "ktup_topn.h"
@@ -54,11 +61,15 @@ namespace {
 constexpr int IB = 64, UB = 64, NW = 16, GS = 4, NBAND = 8;   // GS: golds a sweep launch counts for (further launches take golds
                                                               // 4.., 8.. of the few keys that have them)
 
-// MODE 0: TransE; 1: TransH, both products in the sweep; 2: TransH, w.e from the (relations x candidates) table
+// MODE 0: TransE; 1: TransH, both products in the sweep; 2: TransH, w.e from the (relations x candidates) table;
+// 3: TransR -- slot 0 of the query rows holds the folded c' = M_r^T c, |c|^2 comes from qcc and the candidate term |M_r e|^2 from the
+// (relations x entities) table of ktup_eval_transr_prepare (pitch n_ent) in |e|^2's place, by mode 2's look-up
 template <int NCH_, int MODE_>
 struct FGeom {
   static constexpr int NCH = NCH_, D = 4 * NCH, MODE = MODE_;
-  static constexpr bool TRANSH = MODE == 1, WTAB = MODE == 2;
+  static constexpr bool TRANSH = MODE == 1, WTAB = MODE == 2, RTAB = MODE == 3;
+  static constexpr bool TAB = WTAB || RTAB;                    // a per-(relation, candidate) table is looked up
+  static constexpr bool WTERMS = TRANSH || WTAB;               // the score carries TransH's w terms
   static constexpr int KG = (D + 15) / 16;
   static constexpr bool TAIL1 = NCH - 4 * (KG - 1) == 1;
   static constexpr int KGF = TAIL1 ? KG - 1 : KG;
@@ -85,7 +96,8 @@ struct FArgs {
   float* cnorm;                 // |e|^2 of every candidate, computed ONCE per pass (kg_pass_init_kernel) and read by both kernels
   const int64_t* rel;           // mode 2: the keys' relation ids, the normals' table and w.e of every (relation, candidate)
   const float* Nrm; int64_t ldn; int n_rel;
-  float* wtab; int64_t ldw;
+  float* wtab; int64_t ldw;     // (mode 3: the table of |M_r e|^2, pitch n_ent, read only)
+  const float* qcc;             // mode 3: |c|^2 of every key's unfolded query (transr_query_fold_kernel)
   // exact order near the golds: the raw inputs of the fp64 re-score, the per-key window and the list of undecided comparisons
   int model, d, head;
   const float* E; int64_t lde; const float* R; int64_t ldr; const int64_t* q;
@@ -185,7 +197,7 @@ KTUP_DEV void row_scalars(const v4* c0, const v4* w0, int sub, float& f0, float&
   for (int c = sub; c < NCH; c += 8) {
     const v4 x0 = c0[c];
     s0 += x0 * x0;
-    if (G::MODE != 0 && w0) { const v4 x1 = w0[c]; s1 += x0 * x1; s2 += x1 * x1; }
+    if (G::WTERMS && w0) { const v4 x1 = w0[c]; s1 += x0 * x1; s2 += x1 * x1; }
   }
   f0 = (s0[0] + s0[1]) + (s0[2] + s0[3]); f1 = (s1[0] + s1[1]) + (s1[2] + s1[3]); f2 = (s2[0] + s2[1]) + (s2[2] + s2[3]);
 #pragma unroll
@@ -202,6 +214,7 @@ KTUP_DEV void query_scalars(const FArgs& a, const v4* Q, float* qs, int64_t u0, 
     if (G::WTAB && u0 + row < a.nq) w0 = reinterpret_cast<const v4*>(a.QW + ((u0 + row) * 3 + 2) * a.dq);
     float f0, f1, f2;
     row_scalars<G>(c0, w0, threadIdx.x & 7, f0, f1, f2);
+    if (G::RTAB) f0 = u0 + row < a.nq ? a.qcc[u0 + row] : 0.f;   // slot 0 is the folded query: |c|^2 was taken before the fold
     if ((threadIdx.x & 7) == 0) { qs[row * 4 + 0] = f0; qs[row * 4 + 1] = f1; qs[row * 4 + 2] = f2; }
   }
 }
@@ -232,23 +245,7 @@ KTUP_DEV void tile_dots(const v4* qa, const v4* cb, v4& ce, v4& we) {
 
 // one product of the tile: the `ce` chain of tile_dots alone (the same instructions on the same operands: the same bits)
 template <typename G>
-KTUP_DEV v4 tile_dot1(const v4* qa, const v4* cb) {
-  constexpr int KGF = G::KGF;
-  v4 ce = (v4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int g = 0; g < KGF; ++g) {
-    const v4 ac = qa[4 * g], be = cb[4 * g];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) ce = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[c], be[c], ce, 0, 0, 0);
-  }
-  if (G::TAIL1) {
-    const int kq = (threadIdx.x & 63) >> 4;
-    const float qf = (reinterpret_cast<const float*>(qa - kq + 4 * KGF) + kq)[0];
-    const float be = (reinterpret_cast<const float*>(cb - kq + 4 * KGF) + kq)[0];
-    ce = __builtin_amdgcn_mfma_f32_16x16x4f32(qf, be, ce, 0, 0, 0);
-  }
-  return ce;
-}
+KTUP_DEV v4 tile_dot1(const v4* qa, const v4* cb) { return kg_tile_dot1<G::KGF, G::TAIL1>(qa, cb); }   // (ktup_kg_mc_tile.h: the score kernel's too)
 
 // the same tile with the query-side operands held in registers (the sweep re-uses them for every candidate stage): the MFMA
 // sequence and its operand VALUES are those of tile_dots, so the results are the same bits
@@ -292,8 +289,9 @@ KTUP_DEV void tile_dots_q(const QRegs<G>& q, const v4* cb, v4& ce, v4& we) {
 
 template <typename G>
 KTUP_DEV float pair_score(float ce, float we, float cc, float en, float cw, float ww) {
-  float score = fmaf(-2.f, ce, cc + en);
-  if (G::MODE != 0) score = fmaf(we, fmaf(we, ww - 2.f, 2.f * cw), score);
+  if (G::RTAB) return kg_l2_score(ce, cc, we);                  // `we` carries the table entry |M_r e|^2: the epilogue of pairs_kg_l2_mc_kernel
+  float score = kg_l2_score(ce, cc, en);
+  if (G::WTERMS) score = fmaf(we, fmaf(we, ww - 2.f, 2.f * cw), score);
   return score;
 }
 
@@ -314,7 +312,7 @@ __global__ __launch_bounds__(256) void kg_list_scores_kernel(FArgs a) {
   query_scalars<G>(a, Q, qs, u0, 256);
   __syncthreads();
   if (a.ktol && tid < UB && u0 + tid < a.nq) {                  // T = 2 kappa (|c|^2 + max |e|^2): see the file header
-    const float ww = G::MODE != 0 ? qs[tid * 4 + 2] : 0.f;
+    const float ww = G::WTERMS ? qs[tid * 4 + 2] : 0.f;
     a.ktol[u0 + tid] = 2.f * a.kappa0 * (1.f + ww) * (1.f + ww) * (qs[tid * 4 + 0] + __uint_as_float(*a.enmax));
   }
   // this lane's key (for gathering: lane = (row j of the wave, chunk group))
@@ -322,7 +320,7 @@ __global__ __launch_bounds__(256) void kg_list_scores_kernel(FArgs a) {
   const bool key_on = key_j < a.nq;
   const int64_t g0 = key_on ? a.gold_off[key_j] : 0, ng = key_on ? a.gold_off[key_j + 1] - g0 : 0;
   const int64_t f0_ = (key_on && a.filt_off) ? a.filt_off[key_j] : 0, nf = (key_on && a.filt_off) ? a.filt_off[key_j + 1] - f0_ : 0;
-  const int64_t wrow = (G::WTAB && key_on) ? a.rel[key_j] * a.ldw : 0;
+  const int64_t wrow = (G::TAB && key_on) ? a.rel[key_j] * a.ldw : 0;
   int64_t len = ng + nf, maxlen = len;
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) { const int64_t o = __shfl_xor(maxlen, m, 64); maxlen = o > maxlen ? o : maxlen; }
@@ -346,8 +344,8 @@ __global__ __launch_bounds__(256) void kg_list_scores_kernel(FArgs a) {
       const int c = kq + 4 * k;
       rw[k] = (valid && c < NCH) ? *reinterpret_cast<const v4*>(a.C + (int64_t)cid * a.ldc + 4 * c) : (v4){0.f, 0.f, 0.f, 0.f};
     }
-    en_n = valid ? a.cnorm[cid] : 0.f;                           // the same |e|^2 the sweep reads
-    wt_n = (G::WTAB && valid) ? a.wtab[wrow + cid] : 0.f;         // and the same w.e
+    en_n = (!G::RTAB && valid) ? a.cnorm[cid] : 0.f;             // the same |e|^2 the sweep reads
+    wt_n = (G::TAB && valid) ? a.wtab[wrow + cid] : 0.f;          // and the same w.e (mode 3: |M_r e|^2)
   };
   int32_t cid_cur = list_id(0), cid_nxt = list_id(1);
   list_rows(cid_cur);
@@ -418,7 +416,9 @@ __global__ __launch_bounds__(NW * 64) void kg_count_mc_kernel(FArgs a) {
   constexpr int NCH = G::NCH, P4 = G::P4, QV = G::QV, GMX = GS;
   // what a lane keeps in registers across the stages (128 VGPRs per wave at 16 waves per CU): the gold scores and the three scalars
   // of its four keys, and -- at the narrow widths, one vector per key -- the query operands of its MFMAs (see QR below)
-  constexpr bool QREGS = !G::TRANSH && !(G::WTAB && NCH >= 25);
+  // (mode 3 reads them from LDS at EVERY width: its product is kg_tile_dot1 of ktup_kg_mc_tile.h, the chunked route's own copy, in
+  // every stage loop -- tile_dots_q below is a second chain of the same shape and never forms a TransR score)
+  constexpr bool QREGS = !G::TRANSH && !(G::TAB && NCH >= 25) && !G::RTAB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   v4* Q = reinterpret_cast<v4*>(smem);
   v4* Cd = Q + UB * QV * P4;                                    // [2][IB][P4]
@@ -476,11 +476,12 @@ __global__ __launch_bounds__(NW * 64) void kg_count_mc_kernel(FArgs a) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int ur = 16 * ut + 4 * kq + r;
-    const float T = (a.ktol && u0 + ur < a.nq) ? a.ktol[u0 + ur] : 0.f;
+    // (mode 3 never has a window: T = 0 at compile time, so lo and hi are ONE register per gold)
+    const float T = (!G::RTAB && a.ktol && u0 + ur < a.nq) ? a.ktol[u0 + ur] : 0.f;
 #pragma unroll
     for (int g = 0; g < GN; ++g) { cnt[r][g] = 0; lo[r][g] = gth[ur * GMX + g] - T; hi[r][g] = gth[ur * GMX + g] + T; }
     qsr[r] = *reinterpret_cast<const v4*>(qs + ur * 4);
-    wo[r] = (G::WTAB && u0 + ur < a.nq) ? (int32_t)(a.rel[u0 + ur] * a.ldw) : 0;
+    wo[r] = (G::TAB && u0 + ur < a.nq) ? (int32_t)(a.rel[u0 + ur] * a.ldw) : 0;
   }
   QRegs<G> qr;
   if constexpr (QR) qr.load(qa);
@@ -498,8 +499,11 @@ __global__ __launch_bounds__(NW * 64) void kg_count_mc_kernel(FArgs a) {
   const int64_t band_rows = max((int64_t)0, min((int64_t)a.tiles_per_band * IB, a.n_cand - band_row0));
   const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.C + band_row0 * a.ldc), 0,
                                                                          (int)(band_rows * a.ldc * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsN = __builtin_amdgcn_make_buffer_rsrc(a.cnorm + band_row0, 0, (int)(band_rows * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(G::WTAB ? a.wtab : a.cnorm, 0, G::WTAB ? (int)((int64_t)a.n_rel * a.ldw * 4) : 0,
+  // (mode 3 has no |e|^2 array: an empty range, never loaded from.  Its table's pitch is n_cand itself, so the last partial tile of a
+  // relation reads the next relation's first entries -- lanes the `cand < n_cand` test masks -- and the range ends with the table)
+  const __amdgpu_buffer_rsrc_t rsN = __builtin_amdgcn_make_buffer_rsrc(G::RTAB ? a.wtab : a.cnorm + band_row0, 0, G::RTAB ? 0 : (int)(band_rows * 4),
+                                                                         0x00020000);
+  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(G::TAB ? a.wtab : a.cnorm, 0, G::TAB ? (int)((int64_t)a.n_rel * a.ldw * 4) : 0,
                                                                          0x00020000);
   int voC[NLD];
 #pragma unroll
@@ -518,8 +522,8 @@ __global__ __launch_bounds__(NW * 64) void kg_count_mc_kernel(FArgs a) {
 #pragma unroll
     for (int k = 0; k < NLD; ++k)
       nx[k] = __builtin_bit_cast(v4, __builtin_amdgcn_raw_buffer_load_b128(rsC, voC[k] < 0 ? voC[k] : voC[k] + soC, 0, 0));
-    en_nx = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsN, voN + soN, 0, 0));
-    if constexpr (G::WTAB) {
+    if constexpr (!G::RTAB) en_nx = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsN, voN + soN, 0, 0));
+    if constexpr (G::TAB) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) we_nx[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsW, voW[r] + soN, 0, 0));
     }
@@ -758,9 +762,14 @@ int run_fused(FArgs a, int64_t n_gold, int64_t max_golds, hipStream_t st, const 
   (void)hipFuncSetAttribute((const void*)kg_list_scores_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
   const unsigned qblocks = (unsigned)((a.nq + UB - 1) / UB);
   const int64_t init_work = n_gold > (a.n_cand * 8) ? n_gold : a.n_cand * 8;
-  hipLaunchKernelGGL(kg_unc_reset_kernel, dim3(grid_for((a.unc_nseg + 256) / 256, 64)), dim3(256), 0, st, a.enmax, a.unc_count, a.unc_nseg);
-  hipLaunchKernelGGL(kg_pass_init_kernel, dim3(grid_for((init_work + 255) / 256, 2048)), dim3(256), 0, st, a.counts, n_gold, a.C, a.ldc, G::NCH,
-                     a.n_cand, a.cnorm, a.enmax);
+  if constexpr (G::RTAB) {                                     // no window and no |e|^2 array: the init kernel only clears the counts
+    hipLaunchKernelGGL(kg_pass_init_kernel, dim3(grid_for((n_gold + 255) / 256, 2048)), dim3(256), 0, st, a.counts, n_gold, a.C, a.ldc, 0, (int64_t)0,
+                       (float*)nullptr, (uint32_t*)nullptr);
+  } else {
+    hipLaunchKernelGGL(kg_unc_reset_kernel, dim3(grid_for((a.unc_nseg + 256) / 256, 64)), dim3(256), 0, st, a.enmax, a.unc_count, a.unc_nseg);
+    hipLaunchKernelGGL(kg_pass_init_kernel, dim3(grid_for((init_work + 255) / 256, 2048)), dim3(256), 0, st, a.counts, n_gold, a.C, a.ldc, G::NCH,
+                       a.n_cand, a.cnorm, a.enmax);
+  }
   const int64_t ntiles = (a.n_cand + IB - 1) / IB;
   if constexpr (G::WTAB) hipLaunchKernelGGL((kg_wtab_kernel<G>), dim3((unsigned)ntiles, (unsigned)((a.n_rel + 15) / 16)), dim3(256), 0, st, a);
   a.gscore_out = const_cast<float*>(a.gscore);
@@ -793,6 +802,16 @@ int dispatch_fused(const FArgs& a, int d, int64_t n_gold, int64_t max_golds, hip
 }
 
 size_t pad256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+// TransR's matrix-core instantiations: the widths of transr_pass_mc_route
+int dispatch_transr(const FArgs& a, int d, int64_t n_gold, int64_t max_golds, hipStream_t st, const char* name) {
+  switch (d) {
+    case 64: return run_fused<FGeom<16, 3>>(a, n_gold, max_golds, st, name);
+    case 100: return run_fused<FGeom<25, 3>>(a, n_gold, max_golds, st, name);
+    case 128: return run_fused<FGeom<32, 3>>(a, n_gold, max_golds, st, name);
+    default: return 1;
+  }
+}
 
 
 // mode 2's table: pitch (whole candidate stages) and whether it is used at all -- offsets stay 32-bit, the table below 1 GiB
@@ -892,4 +911,78 @@ extern "C" int ktup_eval_kg_ranks_fused(int model, const float* E, int64_t lde, 
   } else rc = dispatch_fused<1>(a, d, n_gold, max_golds, st, name);
   if (rc == 1) return set_error(KTUP_ERR_UNSUPPORTED, "%s: d=%d is not an instantiated width", name, d);
   return rc;
+}
+
+// ---- TransR (transR.py:80-128 scores, utils/misc.py:125-146 walk): the pass without the score matrix.  Squared L2 on the matrix-core
+// route of ktup_eval_transr_scores (transr_pass_mc_route) is mode 3 of the sweep above; everything else is the pair kernel's list and
+// COUNT forms over the projected table with the keys bucketed by relation (ktup_eval.hip transr_pair_counts).  Declined with
+// KTUP_ERR_UNSUPPORTED before any HIP call: see include/ktup_hip.h.
+static constexpr int TRANSR_MAX_DQ = 256;       // the widest row ktup_eval_transr_prepare projects (inside the pair kernels' 160 KB LDS stage)
+static constexpr int TRANSR_MAX_REL = 16384;    // rel_bucket_kernel's counters live in 64 KB of LDS
+
+extern "C" int ktup_eval_kg_ranks_transr_fused_supported(int d, int l1, int64_t max_golds) {
+  (void)l1; (void)max_golds;
+  return d > 0 && ((d + 3) & ~3) <= TRANSR_MAX_DQ;
+}
+
+extern "C" size_t ktup_eval_kg_ranks_transr_fused_workspace_bytes(int d, int64_t nq, int64_t n_gold, int64_t n_filt, int64_t n_ent, int n_rel) {
+  if (d <= 0 || nq <= 0 || n_ent <= 0 || n_rel <= 0) return 0;
+  // QW | qcc | qrel | gscore | counts | fscore | rel_off | qperm: nothing in nq x n_ent (and nothing per entity at all)
+  return ktup::pad256(ktup_eval_kg_workspace_bytes(d, nq)) + 3 * ktup::pad256((size_t)nq * 4) + 2 * ktup::pad256((size_t)(n_gold > 0 ? n_gold : 1) * 4) +
+         ktup::pad256((size_t)(n_filt > 0 ? n_filt : 1) * 4) + ktup::pad256(((size_t)n_rel + 1) * 4);
+}
+
+extern "C" int ktup_eval_kg_ranks_transr_fused(const float* E, int64_t lde, const float* R, int64_t ldr, const float* M, int64_t ldm, int d,
+                                               int64_t n_ent, int n_rel, const float* ents_ws, const int64_t* q, const int64_t* r, int64_t nq,
+                                               int l1, int head, int descending, const int64_t* filt_off, const int32_t* filt_ids, int64_t n_filt,
+                                               const int64_t* gold_off, const int32_t* gold_ids, int64_t n_gold, int64_t max_golds,
+                                               int32_t* ranks, void* ws, void* stream) {
+  const char* name = "ktup_eval_kg_ranks_transr_fused";
+  using namespace ktup;
+  if (!ents_ws) return set_error(KTUP_ERR_INVALID_ARG, "%s: ents_ws is required (ktup_eval_transr_prepare)", name);
+  if (!ktup_eval_kg_ranks_transr_fused_supported(d, l1, max_golds))
+    return set_error(KTUP_ERR_UNSUPPORTED, "%s: embedding_size %d does not fit the pair kernels' LDS stage", name, d);
+  if ((nq + UB - 1) / UB > 65535 || n_ent >= (1ll << 31) || n_rel > TRANSR_MAX_REL)
+    return set_error(KTUP_ERR_UNSUPPORTED, "%s: sizes out of range for one sweep (%lld keys, %lld entities, %d relations)", name, (long long)nq,
+                     (long long)n_ent, n_rel);
+  const bool mc = transr_pass_mc_route(d, l1, E, lde);
+  // the sweep reads the norm table through ONE 32-bit buffer descriptor (byte offsets of a stage past the last band included) and a
+  // band of the entity table through another
+  if (mc && (((int64_t)n_rel * n_ent + 16 * IB) * 4 >= (1ll << 31) ||
+             ((n_ent + IB * NBAND - 1) / (IB * NBAND) + 1) * IB * lde * 4 >= (1ll << 31)))
+    return set_error(KTUP_ERR_UNSUPPORTED, "%s: the (relations x entities) norm table or a band of the entity table exceeds the 32-bit buffer range", name);
+  KTUP_REQUIRE(nq >= 0 && n_ent > 0 && n_rel > 0 && n_gold >= 0 && n_filt >= 0 && max_golds >= 0, "%s: bad sizes", name);
+  if (nq == 0 || n_gold == 0) return KTUP_OK;
+  KTUP_REQUIRE(E && R && M && q && r && gold_off && gold_ids && ranks && ws && ldm >= (int64_t)d * d, "%s: bad argument", name);
+  KTUP_REQUIRE((filt_off == nullptr) || filt_ids, "%s: filter offsets without ids", name);
+  KTUP_REQUIRE(aligned16(ws) && aligned16(ents_ws), "%s: workspaces must be 16-byte aligned", name);
+  hipStream_t st = (hipStream_t)stream;
+  const int dq = (d + 3) & ~3;
+  char* p = reinterpret_cast<char*>(ws);
+  float* QW = reinterpret_cast<float*>(p); p += pad256(ktup_eval_kg_workspace_bytes(d, nq));
+  float* qcc = reinterpret_cast<float*>(p); p += pad256((size_t)nq * 4);
+  int32_t* qrel = reinterpret_cast<int32_t*>(p); p += pad256((size_t)nq * 4);   // written by the fold kernel (the chunked route's score
+                                                                                // kernel reads it); the pass takes the relation from `r`
+  float* gscore = reinterpret_cast<float*>(p); p += pad256((size_t)n_gold * 4);
+  int32_t* counts = reinterpret_cast<int32_t*>(p); p += pad256((size_t)n_gold * 4);
+  float* fscore = reinterpret_cast<float*>(p); p += pad256((size_t)(n_filt > 0 ? n_filt : 1) * 4);
+  int32_t* rel_off = reinterpret_cast<int32_t*>(p); p += pad256(((size_t)n_rel + 1) * 4);
+  int32_t* qperm = reinterpret_cast<int32_t*>(p);
+  if (int e = kg_query_prep(2, E, lde, R, ldr, M, ldm, d, q, r, nq, head, QW, st, name)) return e;
+  if (mc) {
+    if (int e = transr_query_fold(QW, dq, M, ldm, d, r, nq, qcc, qrel, st, name)) return e;
+    FArgs a{};
+    a.QW = QW; a.dq = dq; a.C = E; a.ldc = lde; a.nq = nq; a.n_cand = n_ent; a.descending = descending;
+    a.gold_off = gold_off; a.gold_ids = gold_ids; a.gscore = gscore; a.filt_off = filt_off; a.filt_ids = filt_ids; a.fscore = fscore;
+    a.counts = counts; a.ranks = ranks; a.dbg = opt_dbg_eval(); a.d = d; a.head = head;
+    a.rel = r; a.n_rel = n_rel; a.wtab = const_cast<float*>(ents_ws); a.ldw = n_ent; a.qcc = qcc;
+    a.ktol = nullptr;                                          // no window: the keys of the scores decide, as on the chunked route
+    return dispatch_transr(a, d, n_gold, max_golds, st, name);
+  }
+  hipLaunchKernelGGL(kg_pass_init_kernel, dim3(grid_for((n_gold + 255) / 256, 2048)), dim3(256), 0, st, counts, n_gold, E, lde, 0, (int64_t)0,
+                     (float*)nullptr, (uint32_t*)nullptr);
+  if (int e = transr_pair_counts(QW, d, ents_ws, n_ent, n_rel, nq, l1, descending, gold_off, gold_ids, filt_off, filt_ids, gscore, fscore, counts,
+                                 r, rel_off, qperm, st, name))
+    return e;
+  return kg_rank_finalize(gold_off, gold_ids, gscore, filt_off, filt_ids, fscore, counts, ranks, nq, n_ent, n_gold, descending, st, name);
 }

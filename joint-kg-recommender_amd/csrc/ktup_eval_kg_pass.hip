@@ -20,7 +20,8 @@
 // the score kernel of chunk c + 1 fills the other buffer: K12 / K13 is bound by writing the matrix, K18 by reading it, and their
 // sum (50 + 19 us per 512 keys at ml1m-kg size) becomes their maximum.  Never while the caller's stream is being captured
 // (fork_side then declines and the chunks run back to back on one stream, as before).  TransR joins the entry point family
-// (ktup_eval_kg_ranks_transr: entity side prepared once per pass by the caller, K14 per chunk).
+// (ktup_eval_kg_ranks_transr: entity side prepared once per pass by the caller, K14 per chunk).  The pass WITHOUT the score matrix
+// is ktup_eval_kg_ranks_transr_fused (ktup_eval_kg_fused.hip); this chunked route stays as its yardstick and for what it declines.
 namespace {
 
 size_t score_bytes(int64_t chunk, int64_t n_cand) { return (((size_t)chunk * (size_t)n_cand * sizeof(float)) + 255) & ~(size_t)255; }

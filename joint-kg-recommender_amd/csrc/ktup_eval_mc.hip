@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "ktup_common.h"
+#include "ktup_kg_mc_tile.h"
 #include "ktup_lane_swap.h"
 #include "ktup_pref_geom.h"
 
@@ -234,22 +235,24 @@ __global__ __launch_bounds__(G::NW * 64) void pairs_kg_l2_mc_kernel(KArgs a) {
   const v4* qa = Q + ((16 * ut + j) * QV) * P4 + kq;
   const v4* cb = Cd + (16 * it + j) * P4 + kq;
   v4 ce = (v4){0.f, 0.f, 0.f, 0.f}, we = ce;
+  if constexpr (!TRANSH) {
+    ce = kg_tile_dot1<KGF, TAIL1>(qa, cb);                     // TransE / TransR: the one product, shared with the pass (ktup_kg_mc_tile.h)
+  } else {
 #pragma unroll
-  for (int g = 0; g < KGF; ++g) {
-    const v4 ac = qa[4 * g], be = cb[4 * g];
-    v4 aw = ac;
-    if (TRANSH) aw = qa[P4 + 4 * g];
+    for (int g = 0; g < KGF; ++g) {
+      const v4 ac = qa[4 * g], be = cb[4 * g], aw = qa[P4 + 4 * g];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      ce = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[c], be[c], ce, 0, 0, 0);
-      if (TRANSH) we = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[c], be[c], we, 0, 0, 0);
+      for (int c = 0; c < 4; ++c) {
+        ce = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[c], be[c], ce, 0, 0, 0);
+        we = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[c], be[c], we, 0, 0, 0);
+      }
     }
-  }
-  if (TAIL1) {
-    const float* qf = reinterpret_cast<const float*>(Q + ((16 * ut + j) * QV) * P4 + 4 * KGF) + kq;
-    const float be = (reinterpret_cast<const float*>(Cd + (16 * it + j) * P4 + 4 * KGF) + kq)[0];
-    ce = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[0], be, ce, 0, 0, 0);
-    if (TRANSH) we = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[4 * P4], be, we, 0, 0, 0);
+    if (TAIL1) {
+      const float* qf = reinterpret_cast<const float*>(Q + ((16 * ut + j) * QV) * P4 + 4 * KGF) + kq;
+      const float be = (reinterpret_cast<const float*>(Cd + (16 * it + j) * P4 + 4 * KGF) + kq)[0];
+      ce = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[0], be, ce, 0, 0, 0);
+      we = __builtin_amdgcn_mfma_f32_16x16x4f32(qf[4 * P4], be, we, 0, 0, 0);
+    }
   }
   const float ee = cs[16 * it + j];
   const int64_t cand = i0 + 16 * it + j;
@@ -261,7 +264,7 @@ __global__ __launch_bounds__(G::NW * 64) void pairs_kg_l2_mc_kernel(KArgs a) {
       cc = a.qcc[u0 + ur];
       en = a.cnorm[(int64_t)a.qrel[u0 + ur] * a.n_cand + cand];
     }
-    float score = fmaf(-2.f, ce[reg], cc + en);
+    float score = kg_l2_score(ce[reg], cc, en);
     if (TRANSH) {
       const float cw = qs[ur * 4 + 1], ww = qs[ur * 4 + 2], ew = we[reg];
       score = fmaf(ew, fmaf(ew, ww - 2.f, 2.f * cw), score);

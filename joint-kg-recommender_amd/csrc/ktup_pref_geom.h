@@ -88,6 +88,14 @@ int kg_valu_counts(int model, const float* QW, int d, const float* C, int64_t ld
                    const int64_t* gold_off, const int32_t* gold_ids, const int64_t* filt_off, const int32_t* filt_ids, float* gscore,
                    float* fscore, int32_t* counts, const int64_t* rel, const float* Nrm, int64_t ldn, int64_t n_rel, float* wtab, int64_t ldw,
                    hipStream_t st, const char* name);
+// ktup_eval.hip, for TransR's pass (ktup_eval_kg_fused.hip): which shape `ents_ws` holds, the query fold of the matrix-core route, and
+// the pair form's list scores and counts with the keys bucketed by relation
+bool transr_pass_mc_route(int d, int l1, const float* E, int64_t lde);
+int transr_query_fold(float* QW, int dq, const float* M, int64_t ldm, int d, const int64_t* r, int64_t nq, float* qcc, int32_t* qrel,
+                      hipStream_t st, const char* name);
+int transr_pair_counts(const float* QW, int d, const float* PE, int64_t n_ent, int n_rel, int64_t nq, int l1, int descending,
+                       const int64_t* gold_off, const int32_t* gold_ids, const int64_t* filt_off, const int32_t* filt_ids, float* gscore,
+                       float* fscore, int32_t* counts, const int64_t* rel, int32_t* rel_off, int32_t* qperm, hipStream_t st, const char* name);
 // ktup_eval_kg_fused.hip: the last step of a count pass -- ranks[g] = counts[g] - (filtered ids and other golds of the key ordered
 // before gold g, from the list scores gscore / fscore by their 64-bit keys), -1 for a gold that is itself filtered; counts <- 0
 int kg_rank_finalize(const int64_t* gold_off, const int32_t* gold_ids, const float* gscore, const int64_t* filt_off, const int32_t* filt_ids,

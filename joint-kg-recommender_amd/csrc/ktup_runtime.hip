@@ -63,6 +63,8 @@ Option g_opts[] = {
                                                                             // packed into four, at P <= 16 three, by ktup_split_plan.h)
     {"transd_fused", "KTUP_TRANSD_FUSED", {env_int("KTUP_TRANSD_FUSED", 1)}},         // 0: the TransD link-prediction pass keeps the chunked score-matrix route; read by the callers
                                                                             // (ktup_get_option; ops.eval_kg_ranks_transd), who otherwise take ktup_eval_kg_ranks_transd_fused: the same ranks
+    {"transr_fused", "KTUP_TRANSR_FUSED", {env_int("KTUP_TRANSR_FUSED", 1)}},         // 0: the TransR / CKE link-prediction pass keeps the chunked score-matrix route; read by the callers
+                                                                            // (ops.eval_kg_ranks_transr), who otherwise take ktup_eval_kg_ranks_transr_fused where it is the default: the same ranks
 };
 Option* find(const char* name) {
   for (auto& o : g_opts)

@@ -691,17 +691,49 @@ def eval_kg_ranks(E, R, N, q, r, l1, head, descending, gold_off, gold_ids, filt_
     return ranks
 
 
+# l1 -> whether the TransR / CKE pass without the score matrix is the default for that distance: only where its median gain over the
+# chunked route exceeded the larger spread in both runs of tools/transr_pass_time.py (profiles/transr_pass_times.txt)
+TRANSR_FUSED_DEFAULT = {False: True, True: True}
+TRANSR_PASS_ROUTE = [None]       # the route the last eval_kg_ranks_transr call took (the drivers log it)
+
+
 @torch.no_grad()
-def eval_kg_ranks_transr(E, R, M, q, r, l1, head, descending, gold_off, gold_ids, filt_off=None, filt_ids=None, ents=None, chunk=512):
-    """eval_kg_ranks for TransR (ktup_eval_kg_ranks_transr): K14 per chunk of keys against the entity side `ents`
-    (eval_transr_entities, once per pass) + K18, the loop under the C ABI."""
+def eval_kg_ranks_transr(E, R, M, q, r, l1, head, descending, gold_off, gold_ids, filt_off=None, filt_ids=None, ents=None, chunk=512,
+                         fused=None):
+    """eval_kg_ranks for TransR -> int32 [gold_off[-1]]; -1 = a gold id that is itself filtered.  Two routes with the same integers:
+    the pass without the score matrix (ktup_eval_kg_ranks_transr_fused: all keys in one go, ranks from counts formed where the scores
+    are made) and the chunked one (ktup_eval_kg_ranks_transr: K14 per chunk of keys + K18, the loop under the C ABI), both against
+    the entity side `ents` (eval_transr_entities, once per pass; the pass prepares it itself when it is None).  fused=False: chunked;
+    True: the pass wherever it covers the shape; None: the pass where it is the default (TRANSR_FUSED_DEFAULT per distance, library
+    option transr_fused / KTUP_TRANSR_FUSED=0: chunked)."""
     dev = _dev(_table('entity table', E)); _table('relation table', R); _table('projection table', M)
     nq = q.numel(); q = _ids('q', q, dev); r = _ids('r', r, dev, nq)
     filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
     _csr_offsets('eval_kg_ranks_transr', nq, gold_off, filt_off)
     if ents is not None and (ents.shape != (E.shape[0], E.shape[1], R.shape[0]) or ents.l1 != bool(l1)):
         raise L.KtupError('prepared entity side does not match the tables / distance kind')
-    ranks = torch.empty(max(gold_ids.numel(), 1), dtype=torch.int32, device=dev)
+    n_gold = gold_ids.numel()
+    ranks = torch.empty(max(n_gold, 1), dtype=torch.int32, device=dev)
+    if fused is None:
+        fused = TRANSR_FUSED_DEFAULT[bool(l1)] and L.get_option('transr_fused') != 0
+    if fused and nq > 0 and n_gold > 0:
+        mg = _max_golds(gold_off)
+        lib = L.load()
+        if lib.ktup_eval_kg_ranks_transr_fused_supported(E.shape[1], int(bool(l1)), mg):
+            n_filt = 0 if filt_ids is None else filt_ids.numel()
+            fws = _scratch(lib.ktup_eval_kg_ranks_transr_fused_workspace_bytes(E.shape[1], nq, n_gold, n_filt, E.shape[0], R.shape[0]), dev)
+            try:
+                if ents is None:                       # (a catalogue ktup_eval_transr_prepare declines: the chunked route, which needs none)
+                    ents = eval_transr_entities(E, M, R.shape[0], l1)
+                L.call('ktup_eval_kg_ranks_transr_fused', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0), E.shape[1], E.shape[0],
+                       R.shape[0], _p(ents.ws), _p(q), _p(r), nq, int(bool(l1)), int(head), int(bool(descending)), _p(filt_off), _p(filt_ids),
+                       n_filt, _p(gold_off), _p(gold_ids), n_gold, mg, _p(ranks), _p(fws), _stream(dev))
+                TRANSR_PASS_ROUTE[0] = 'no score matrix (ktup_eval_kg_ranks_transr_fused)'
+                return ranks
+            except L.KtupError as e:
+                if e.code != L.ERR_UNSUPPORTED:        # sizes the pass declines (see include/ktup_hip.h): the chunked route below
+                    raise
+    TRANSR_PASS_ROUTE[0] = 'chunked score matrix (ktup_eval_kg_ranks_transr)'
     chunk = max(1, min(int(chunk), max(nq, 1)))
     ws = _scratch(L.load().ktup_eval_kg_ranks_transr_workspace_bytes(E.shape[1], E.shape[0], R.shape[0], chunk), dev)
     L.call('ktup_eval_kg_ranks_transr', _p(E), E.stride(0), _p(R), R.stride(0), _p(M), M.stride(0), E.shape[1], E.shape[0], R.shape[0],

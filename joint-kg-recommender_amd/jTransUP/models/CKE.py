@@ -86,6 +86,13 @@ class CKE(nn.Module, GradToggle):
         """Entity side of evaluateHead / evaluateTail, once per evaluation pass (`ents=`)."""
         return ops.eval_transr_entities(self.ent_embeddings.weight, self.proj_embeddings.weight, self.rel_embeddings.weight.shape[0], self.L1_flag)
 
+    def rank_entities(self, q, r, head, descending, gold_off, gold_ids, filt_off=None, filt_ids=None, all_e_ids=None, ents=None):
+        """A whole evaluateHead / evaluateTail pass + the filtered gold ranks of utils/misc.py:125-146 in one call
+        (ops.eval_kg_ranks_transr), over the entity table INCLUDING the pad row like the two methods below (all_e_ids is ignored,
+        as they ignore it)."""
+        return ops.eval_kg_ranks_transr(self.ent_embeddings.weight, self.rel_embeddings.weight, self.proj_embeddings.weight, q, r,
+                                        self.L1_flag, head, descending, gold_off, gold_ids, filt_off, filt_ids, ents=ents)
+
     def evaluateHead(self, t, r, all_e_ids=None, ents=None):
         """CKE.py:155-178 over the entity table INCLUDING the pad row."""
         return ops.eval_transr(self.ent_embeddings.weight, self.rel_embeddings.weight, self.proj_embeddings.weight, t, r, self.L1_flag,

@@ -98,8 +98,8 @@ def evaluateKG(FLAGS, model, eval_head_iter, eval_tail_iter, eval_head_dict, eva
     remap = None if FLAGS.share_embeddings else e_map      # :125,140 (identity for id-ordered map files)
     from jTransUP.models._shard_eval import kg_shard_fn
     kw = {'ents': model.prepare_entities()} if hasattr(model, 'prepare_entities') else {}       # CKE: TransR's entity side, once
-    # jTransUP / CFKG: the whole pass -- scores and filtered gold ranks -- behind one call per direction (model.rank_entities)
-    rank = (lambda head: (lambda q, r, desc, go, gi, fo, fi: model.rank_entities(q, r, head, desc, go, gi, fo, fi, all_e_ids=all_e_var))) \
+    # jTransUP / CFKG / CKE: the whole pass -- scores and filtered gold ranks -- behind one call per direction (model.rank_entities)
+    rank = (lambda head: (lambda q, r, desc, go, gi, fo, fi: model.rank_entities(q, r, head, desc, go, gi, fo, fi, all_e_ids=all_e_var, **kw))) \
         if hasattr(model, 'rank_entities') else (lambda head: None)
     native = getattr(model, '_shard_native', None)
     if native is not None and not is_report:
@@ -376,6 +376,10 @@ def run(only_forward=False):
     else:
         train_loop(FLAGS, model, trainer, rating_train_dataset, triple_train_dataset, rating_eval_datasets, triple_eval_datasets,
                    e_map, i_map, ikg_map, logger, vis=vis, is_report=False)
+    if FLAGS.model_type == 'cke':
+        from jTransUP.hip import ops
+        if ops.TRANSR_PASS_ROUTE[0] is not None:
+            logger.info('CKE link-prediction pass: {} (KTUP_TRANSR_FUSED=0 keeps the chunked route).'.format(ops.TRANSR_PASS_ROUTE[0]))
     if vis is not None:
         vis.log('Finish!', win_name='Best Performances')
 

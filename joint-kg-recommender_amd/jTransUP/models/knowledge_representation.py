@@ -138,6 +138,10 @@ def train_loop(FLAGS, model, trainer, train_dataset, eval_datasets, entity_total
         from jTransUP.hip import ops
         if ops.TRANSD_PASS_ROUTE[0] is not None:
             logger.info('TransD link-prediction pass: {} (KTUP_TRANSD_FUSED=0 keeps the chunked route).'.format(ops.TRANSD_PASS_ROUTE[0]))
+    if FLAGS.model_type == 'transr':
+        from jTransUP.hip import ops
+        if ops.TRANSR_PASS_ROUTE[0] is not None:
+            logger.info('TransR link-prediction pass: {} (KTUP_TRANSR_FUSED=0 keeps the chunked route).'.format(ops.TRANSR_PASS_ROUTE[0]))
     trainer.save(trainer.checkpoint_path + '_final')      # knowledge_representation.py:219
 
 

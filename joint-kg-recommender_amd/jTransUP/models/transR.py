@@ -52,7 +52,8 @@ class TransRModel(nn.Module, GradToggle):
         return ops.eval_transr(E, R, M, h, r, self.L1_flag, head=False, ents=ents)
 
     def rank_entities(self, q, r, head, descending, gold_off, gold_ids, filt_off=None, filt_ids=None, ents=None):
-        """A whole evaluateHead / evaluateTail pass + the filtered gold ranks of utils/misc.py:125-146 in one call (K14 + K18 per
-        chunk of 512 keys under the C ABI, the rank kernel of a chunk beside the score kernel of the next)."""
+        """A whole evaluateHead / evaluateTail pass + the filtered gold ranks of utils/misc.py:125-146 in one call: the pass without
+        the score matrix where it is the default (ops.TRANSR_FUSED_DEFAULT, option transr_fused), else K14 + K18 per chunk of 512
+        keys under the C ABI, the rank kernel of a chunk beside the score kernel of the next."""
         E, R, M = self._tables()
         return ops.eval_kg_ranks_transr(E, R, M, q, r, self.L1_flag, head, descending, gold_off, gold_ids, filt_off, filt_ids, ents=ents)
