@@ -614,8 +614,31 @@ int ktup_feed_rec(const int64_t* col_u, const int64_t* col_i, int64_t n_rows, in
 int ktup_feed_kg(const int64_t* col_h, const int64_t* col_t, const int64_t* col_r, int64_t n_rows, int64_t B, int64_t* cursor,
                  uint64_t* offset_dev, int64_t n_ent, int64_t n_rel, const uint64_t* sorted_keys, int64_t n_keys, uint64_t seed,
                  int64_t* h2, int64_t* t2, int64_t* r2, int32_t* fail_count, void* stream);
+/* Feed, joint baselines (csrc/ktup_feed_joint.hip): what coFM / CKE / CFKG still did on the host between a feed launch and their
+ * step kernel.  One launch each, every argument static (graph-replayable), no memset, no scratch that outlives the launch.
+ *
+ * ktup_feed_remap_ids -- in place x[k] = row_of_id[x[k]] over a[0, na) and, when b is not NULL, b[0, nb): raw item / entity ids ->
+ * rows of the joint table under -share_embeddings (knowledgable_recommendation.py:326-328 `[i_map[i] for i in ...]`, :352-356
+ * `[e_map[e] for e in ...]`).  An id outside [0, n_ids_in_map), or one whose entry is negative, becomes row 0 and bumps
+ * *fail_count (int32, may be NULL) -- the samplers' contract: never an out-of-range row, the host checks the counter afterwards.
+ *
+ * ktup_feed_align_lists -- the alignment lists of a step (knowledgable_recommendation.py:28-37 getMappedEntities when
+ * ids_are_entities == 0, :39-48 getMappedItems when != 0, called at :324 / :350): over the DISTINCT values id of a[0, na) and
+ * b[0, nb) (b may be NULL with nb == 0) with 0 <= id < n_partner and partner[id] >= 0, the pair (id, partner[id]) is written exactly
+ * once -- entity id to e_ids[k], item id to i_ids[k], k < *n_out, in no particular order -- and *n_out is set to their number (0 is
+ * a valid result: the list buffers are then untouched).  `cap`: capacity of e_ids / i_ids, cap >= na + nb.  The dedupe is an
+ * open-addressing table in the LDS of ONE workgroup, so nothing has to be reset between launches:
+ * ktup_feed_align_lists_workspace_bytes is 0 and `ws` is not read.  ktup_feed_align_lists_supported(n_ids): 1 for 1 <= n_ids <=
+ * 16384 (a 128 KiB table of 32768 slots at most half full; a workgroup may hold 160 KiB), else 0 and the call is
+ * KTUP_ERR_UNSUPPORTED.  n_partner < 2^31.  Everything else that cannot work is KTUP_ERR_INVALID_ARG before any launch.       */
+int ktup_feed_remap_ids(const int64_t* row_of_id, int64_t n_ids_in_map, int64_t* a, int64_t na, int64_t* b, int64_t nb,
+                        int32_t* fail_count, void* stream);
+int ktup_feed_align_lists_supported(int64_t n_ids);
+size_t ktup_feed_align_lists_workspace_bytes(int64_t n_ids);
+int ktup_feed_align_lists(const int64_t* a, int64_t na, const int64_t* b, int64_t nb, const int64_t* partner, int64_t n_partner,
+                          int ids_are_entities, int64_t cap, int64_t* n_out, int64_t* e_ids, int64_t* i_ids, void* ws, void* stream);
 
-/* ------------------------------------------- K20  global-norm clip + dense optimizer step
+/* ------------------------------------------- K20 global-norm clip + dense optimizer step
  * Replaces   torch.nn.utils.clip_grad_norm(params, max_norm); optimizer.step()
  * (item_recommendation.py:189-192, knowledge_representation.py:209-211, knowledgable_recommendation.py:399-401) for the
  * optimizers of utils/trainer.py:63-77 with weight_decay = l2_lambda, in two launches over a list of tables.

@@ -152,6 +152,10 @@ SIGNATURES = {
     'ktup_negsample_kg': [c_p, c_p, c_p, c_l, c_l, c_l, c_p, c_l, c_u, c_u, c_p, c_p, c_p, c_p],
     'ktup_feed_rec': [c_p, c_p, c_l, c_l, c_p, c_p, c_l, c_p, c_l, c_u, c_i, c_p, c_p, c_p, c_p, c_p],
     'ktup_feed_kg': [c_p, c_p, c_p, c_l, c_l, c_p, c_p, c_l, c_l, c_p, c_l, c_u, c_p, c_p, c_p, c_p, c_p],
+    'ktup_feed_remap_ids': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p],
+    'ktup_feed_align_lists_supported': [c_l],
+    'ktup_feed_align_lists_workspace_bytes': [c_l],
+    'ktup_feed_align_lists': [c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_l, c_p, c_p, c_p, c_p, c_p],
     'ktup_score_transd_fwd': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_p, c_p],
     'ktup_score_transd_bwd': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     'ktup_eval_transd_workspace_bytes': [c_i, c_l],
@@ -193,7 +197,8 @@ _RESTYPE = {'ktup_last_error': ctypes.c_char_p, 'ktup_shard_reduce_list_len': ct
             'ktup_eval_kg_ranks_transd_workspace_bytes': ctypes.c_size_t, 'ktup_eval_dot_topk_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_cfkg_topk_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_kg_ranks_transd_fused_workspace_bytes': ctypes.c_size_t,
-            'ktup_eval_kg_ranks_transr_fused_workspace_bytes': ctypes.c_size_t}
+            'ktup_eval_kg_ranks_transr_fused_workspace_bytes': ctypes.c_size_t,
+            'ktup_feed_align_lists_workspace_bytes': ctypes.c_size_t}
 
 _lib = None
 

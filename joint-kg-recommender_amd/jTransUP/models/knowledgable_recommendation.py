@@ -190,7 +190,25 @@ def train_loop(FLAGS, model, trainer, rating_train_dataset, triple_train_dataset
         from jTransUP.utils.fast_train_dot import BaselineJointStepper
         stepper = baseline = BaselineJointStepper(model, trainer, FLAGS, FLAGS.batch_size)
         logger.info('GPU-resident training step enabled (KTUP_FAST_TRAIN=0 selects the autograd route).')
-        if FLAGS.device_sampling:
+        want_feed = FLAGS.device_sampling and os.environ.get('KTUP_BASELINE_FEED', '0') == '1' and baseline.world == 1
+        if want_feed:
+            baseline.set_id_maps(i_map, e_map, ikg_map, item_total, entity_total)
+            want_feed = baseline.maps_cover('rec') and baseline.maps_cover('kg')     # (a gap in a map: the host route's KeyError stays)
+        if want_feed:
+            # KTUP_BASELINE_FEED=1 (opt-in): batches, negatives, joint-table rows and alignment lists on the device, as for jtransup
+            from jTransUP.utils.device_sampler import DeviceSampler
+            from jTransUP.utils.fast_train import DeviceFeeder
+            sampler = DeviceSampler(D.DEV, seed=FLAGS.seed)
+            sampler.set_rating_dicts(model.user_total, item_total, all_rating_dicts)
+            known = None
+            if FLAGS.filter_wrong_corrupted:
+                known = [triple_train_list] + [[(h, t, r) for (t, r), hs in d[4].items() for h in hs] for d in triple_eval_datasets]
+            sampler.set_triples(entity_total, model.rel_total, known)
+            rec_feed = DeviceFeeder(rating_train_list, FLAGS.batch_size, D.DEV, FLAGS.negtive_samples, seed=FLAGS.seed)
+            kg_feed = DeviceFeeder(triple_train_list, FLAGS.batch_size, D.DEV, FLAGS.negtive_samples, seed=FLAGS.seed + 1)
+            stepper.attach_feeds(sampler, rec=rec_feed, kg=kg_feed)
+            logger.info('Training data and negative sampling are device-resident (-device_sampling).')
+        elif FLAGS.device_sampling:
             logger.info('-device_sampling: the joint baselines take host-fed batches only; running as under -nodevice_sampling.')
     D.require_stepper_for_replicas(stepper, 'jtransup -noshare_embeddings, cofm, cke, cfkg')
     logger.info('Training.')
@@ -246,12 +264,25 @@ def train_loop(FLAGS, model, trainer, rating_train_dataset, triple_train_dataset
                     return kind, None                      # ten steps in one replay; losses are summed on the device
                 stepper.fed_step(kind)
                 return kind, None                          # (stepper.take_sums)
+            # a kind that cannot be fed is host-DRIVEN on the device: same feeder, same sampler, ids handed over per step (for the joint
+            # baselines with the id handling of the branch below: alignment lists from the raw ids, then rows of the joint table)
             if is_rec:
                 u, pi = rec_feed.next_cols()
-                return 'rec', stepper.rec_step(u, pi, sampler.sample_rec(u, pi))
+                ni = sampler.sample_rec(u, pi)
+                if baseline is None:
+                    return 'rec', stepper.rec_step(u, pi, ni)
+                align = getMappedEntities(pi.tolist() + ni.tolist(), i_map, ikg_map) if baseline.align else None
+                if baseline.remaps:
+                    pi, ni = baseline.id_rows['rec'][pi], baseline.id_rows['rec'][ni]
+                return 'rec', stepper.rec_step(u, pi, ni, align=align)
             ph, pt, pr = kg_feed.next_cols()               # (h, t, r): tail before relation, like the files
             nh, nt = sampler.sample_kg(ph, pt, pr)
-            return 'kg', stepper.kg_step(ph, pt, pr, nh, nt, pr)
+            if baseline is None:
+                return 'kg', stepper.kg_step(ph, pt, pr, nh, nt, pr)
+            align = getMappedItems(ph.tolist() + pt.tolist() + nh.tolist() + nt.tolist(), e_map, ikg_map) if baseline.align else None
+            if baseline.remaps:
+                ph, pt, nh, nt = (baseline.id_rows['kg'][x] for x in (ph, pt, nh, nt))
+            return 'kg', stepper.kg_step(ph, pt, pr, nh, nt, pr, align=align)
         if baseline is not None:                           # coFM / CKE / CFKG: the id handling of the autograd route below, then the stepper
             if is_rec:
                 u, pi, ni = getNegRatings(next(rating_train_iter), item_total, all_dicts=all_rating_dicts)

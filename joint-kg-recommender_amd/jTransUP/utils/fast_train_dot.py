@@ -7,8 +7,13 @@ gradients back into the gathered rows -- and ONE launch: ktup_train_dot_step (in
 ktup_optim_clip_step.  The kg side takes what exists: ktup_train_kg_step (TransE) for coFM, the TransR launches of KGStepper for
 CKE.  coFM with its own item table adds the alignment term of knowledgable_recommendation.py:385-390 to EVERY step:
 ktup_reg_align_pairs, whose id lists the host builds exactly as the autograd route does (getMappedEntities / getMappedItems on the
-global batch) and copies, with their length, into fixed buffers outside the graph.  CFKG's rec step is a translation, not an
+global batch) and copies, with their length, into fixed buffers outside the graph -- or, on a device-fed step, ktup_feed_align_lists
+builds in those buffers from the batch the feed launch drew.  CFKG's rec step is a translation, not an
 inner product (user + buy - item-entity, CFKG.py:66-80): ONE launch of its own, ktup_train_cfkg_rec_step; its kg step is coFM's.
+
+Device-fed steps (-device_sampling, `attach_feeds` + `set_id_maps`): feed launch -> [ktup_feed_remap_ids: raw ids -> rows of the joint
+table, coFM -share_embeddings and CFKG] -> step launch -> [ktup_feed_align_lists + ktup_reg_align_pairs, coFM with its own item table]
+-> clip + optimizer launch, one graph per step kind and one per cycle of steps (`fed_step`, `fed_cycle` of utils/fast_train.py).
 
 rec step:  bprLoss(pos, neg, target)                                                   [+ norm_lambda * pNormLoss(ent rows, item rows)]
 kg step:   kg_lambda * (marginLoss(pos, neg, margin) + normLoss(ent rows) + normLoss(rel rows))     [+ the same alignment term]
@@ -100,12 +105,12 @@ class BaselineJointStepper(_StepperBase):
                 nbytes = L.load().ktup_score_transr_workspace_bytes(2 * B, R.shape[0])
                 self.rws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=self.dev)
             self.align = False
-            self.fused_step = False                                     # host-fed only
-            # The kg step is never captured: the relation-bucketed TransR kernels (d = 64, 100, 128) clear their counters in the
+            self.fused_step = False                                     # (`can_feed` decides per kind here, not `_feedable`)
+            # The HOST-FED kg step is never captured: the relation-bucketed TransR kernels (d = 64, 100, 128) clear their counters in the
             # workspace with hipMemsetAsync, and a captured memset node whose destination lies inside a pooled allocation writes garbage
             # from its second replay on -- the bucket kernels then index past the workspace.  The rec step replays.
             # (With `transr_step` the kg step is ktup_train_transr_step, which has no memset and replays safely; it is still
-            # issued eagerly here because the suite pins this stepper's graphs to {'rec'}.)
+            # issued eagerly here because the suite pins this stepper's graphs to {'rec'}; the device-fed kg step is captured, `_fed`.)
             self.never_captured = frozenset(['kg'])
         elif self.cfkg:
             if I is not E:
@@ -114,7 +119,7 @@ class BaselineJointStepper(_StepperBase):
             touch = {'rec': (U, E, R), 'kg': (E, R)}                    # the buy relation is a row of R: R wakes with either kind
             self.align = False
             self.kg_fused = bool(self.want_fused and L.load().ktup_train_step_supported(2, d, 0))
-            self.fused_step = False                                     # host-fed only
+            self.fused_step = False
         else:
             bu, bi, gb = m.user_bias.weight, m.item_bias.weight, m.bias
             shared = I is E
@@ -122,7 +127,11 @@ class BaselineJointStepper(_StepperBase):
             self.align = not shared                                     # :385-390, coFM with its own item table
             touch = {'rec': (U, I, bu, bi, gb) + ((E,) if self.align else ()), 'kg': (E, R) + ((I,) if self.align else ())}
             self.kg_fused = bool(self.want_fused and L.load().ktup_train_step_supported(2, d, 0))
-            self.fused_step = False                                     # host-fed only: the alignment lists are built on the host
+            self.fused_step = False
+        self.remaps = self.cfkg or (not self.cke and I is E)             # the step kernels read rows of the joint table
+        self.id_rows = {}                                               # kind -> raw id -> joint row (int64, device; None: a gap)
+        self.partner = {}                                               # kind -> raw id -> aligned id of the other space, or -1
+        self._align_lists = {}
         self._touch = touch
         self._views = {id(t): t.grad for t in self.tabs}                # ReplicaGradSync's views into the flat bucket
         self._awake = set()
@@ -155,11 +164,122 @@ class BaselineJointStepper(_StepperBase):
         self._keys = None
         self.trainer.fused._plan = None
 
-    def attach_feeds(self, sampler, **feeds):
-        raise L.KtupError('the joint baselines take host-fed batches only')
+    # ------------------------------------------------------------------------------------------------ device-fed steps
+    def set_id_maps(self, i_map, e_map, ikg_map, n_items=None, n_ent=None):
+        """The run's id maps (load_kg_rating_data.load_data: i_map / e_map = raw item / entity id -> index of the joint vocabulary,
+        ikg_map = index -> (entity id or -1, item id or -1)) as device tables, once per run:
+        `id_rows[kind]`  raw id -> row of the joint table (coFM -share_embeddings, CFKG; what `[i_map[i] for i in ...]` does per step),
+        `partner[kind]`  raw id -> the aligned id of the other space or -1 (coFM with its own item table; getMappedEntities /
+                         getMappedItems per step).
+        kind 'rec' is keyed by item ids, 'kg' by entity ids.  An id in [0, n) without a joint row leaves `id_rows[kind]` None: the
+        kind is not fed (the host route raises KeyError on such an id)."""
+        i64 = dict(dtype=torch.int64, device=self.dev)
+        sizes = {'rec': len(i_map) if n_items is None else int(n_items), 'kg': len(e_map) if n_ent is None else int(n_ent)}
+        maps = {'rec': i_map, 'kg': e_map}
+        self.id_rows, self.partner = {}, {}
+        if self.remaps:
+            rows_total = self.m.ent_embeddings.weight.shape[0]
+            for kind, mp in maps.items():
+                rows = [mp.get(x, -1) for x in range(sizes[kind])]
+                if any(not isinstance(r, int) or r < 0 for r in rows):
+                    self.id_rows[kind] = None
+                    continue
+                if max(rows) >= rows_total:
+                    raise L.KtupError('%s id map points at row %d of a table of %d rows' % (kind, max(rows), rows_total))
+                self.id_rows[kind] = torch.tensor(rows, **i64)
+        if self.align:
+            limit = {'rec': self.m.ent_embeddings.weight.shape[0], 'kg': self.m.item_embeddings.weight.shape[0]}
+            for kind, mp in maps.items():
+                mine, other = (1, 0) if kind == 'rec' else (0, 1)      # position of the id's own space / its partner's in a pair
+                out, ok = [], True
+                for x in range(sizes[kind]):
+                    pair = ikg_map[mp[x]] if x in mp else None
+                    out.append(-1 if pair is None else int(pair[other]))
+                    # the lists the host builds carry the pair's own id of x; it is x itself in every vocabulary load_data builds
+                    ok = ok and (pair is None or pair[other] == -1 or pair[mine] == x)
+                if out and max(out) >= limit[kind]:
+                    raise L.KtupError('%s alignment map points at row %d of a table of %d rows' % (kind, max(out), limit[kind]))
+                self.partner[kind] = torch.tensor(out, **i64) if ok else None
+        self._feed_ok = {}
+        self._keys = None
+
+    def maps_cover(self, kind):
+        """Whether `set_id_maps` gave this kind every table its steps need (device-fed or host-driven on the device)."""
+        return (not self.remaps or self.id_rows.get(kind) is not None) and (not self.align or self.partner.get(kind) is not None)
 
     def can_feed(self, kind):
-        return False
+        """Per kind: one process, a step that reads nothing but the [pos ; neg] id arrays the feed launch fills (the rec step always;
+        the kg step where it is ONE launch -- the multi-launch sequences read `ht4`), the id tables of `set_id_maps` covering every
+        id the sampler draws, and an id count ktup_feed_align_lists takes."""
+        ok = self._feed_ok.get(kind)
+        if ok is None:
+            ok = kind in self._feeds and self.world == 1 and self.maps_cover(kind)
+            if ok and kind == 'kg':
+                ok = self.transr_step if self.cke else self.kg_fused
+            sm = self._sampler
+            if ok and self.remaps:
+                ok = (sm.n_items if kind == 'rec' else sm.n_ent) <= self.id_rows[kind].numel()
+            elif ok:                                                    # raw ids ARE the rows the step kernels read
+                ok = sm.n_items <= self.m.item_embeddings.weight.shape[0] if kind == 'rec' else sm.n_ent <= self.m.ent_embeddings.weight.shape[0]
+            if ok and self.align:
+                n_ids = (2 if kind == 'rec' else 4) * self.B
+                ok = n_ids <= self.al_cap and bool(L.load().ktup_feed_align_lists_supported(n_ids))
+            ok = self._feed_ok[kind] = bool(ok)
+        return ok
+
+    def _make_feed(self, kind, st):
+        """The feed launch, then -- where the step kernels read rows of the joint table -- the raw ids it wrote mapped in place."""
+        feed = _StepperBase._make_feed(self, kind, st)
+        if not (self.remaps and self.can_feed(kind)):
+            return feed
+        tab = self.id_rows[kind]
+        a, b = (self.i2, None) if kind == 'rec' else (self.h2, self.t2)
+        remap = L.bind('ktup_feed_remap_ids', _p(tab), tab.numel(), _p(a), a.numel(), None if b is None else _p(b),
+                       0 if b is None else b.numel(), _p(self._sampler.fail), st)
+
+        def run():
+            feed()
+            remap()
+        return run
+
+    def _bind_feeds(self, st):
+        _StepperBase._bind_feeds(self, st)
+        self._align_lists = {}
+        if not self.align:
+            return
+        cap = self.al_cap
+        for kind in self._feeds:
+            if not self.can_feed(kind):
+                continue
+            tab = self.partner[kind]
+            a, b = (self.i2, None) if kind == 'rec' else (self.h2, self.t2)
+            self._align_lists[kind] = L.bind('ktup_feed_align_lists', _p(a), a.numel(), None if b is None else _p(b),
+                                             0 if b is None else b.numel(), _p(tab), tab.numel(), int(kind == 'kg'), cap, _p(self._al),
+                                             _p(self._al[1:]), _p(self._al[1 + cap:]), None, st)
+
+    def _asleep(self, kind):
+        return any(id(t) not in self._awake for t in self._touch[kind])
+
+    def _fed(self, kinds, run, cycle=False):
+        if cycle and any(self._asleep(k) for k in kinds):
+            # A cycle never wakes a table: waking drops the graphs, so the cycle could not run anyway, and a table must join the
+            # optimizer step with the first step of its kind that actually runs -- not when a cycle that holds the kind is asked for
+            return 0
+        if not cycle:
+            self._wake(kinds[0])
+        held = self.never_captured
+        if self.cke and self.transr_step:
+            self.never_captured = frozenset()       # ktup_train_transr_step: no memset, no scratch -- the fed kg step replays
+        try:
+            return run()
+        finally:
+            self.never_captured = held
+
+    def fed_step(self, kind):
+        return self._fed((kind,), lambda: _StepperBase.fed_step(self, kind))
+
+    def fed_cycle(self, kinds):
+        return self._fed(kinds, lambda: _StepperBase.fed_cycle(self, kinds), cycle=True)
 
     # ------------------------------------------------------------------------------------------------ launch plans
     def _bind(self, st):
@@ -215,13 +335,17 @@ class BaselineJointStepper(_StepperBase):
     def _finish(self, kind, n_slots, scale):
         """Alignment launch (own item table), optimizer launch, the step's loss."""
         if self.align:
+            if self._acc_on:                                            # a fed step: the lists of the batch the feed launch drew
+                self._align_lists[kind]()
             self._align()
-        self._optimizer_launches(loss=(_p(self.loss), n_slots, scale, _p(self.out[kind]), None))
+        self._optimizer_launches(loss=(_p(self.loss), n_slots, scale, _p(self.out[kind]), None if self.align else self._acc_ptr(kind)))
         if not self.align:
             return self.out[kind]
         # the alignment term is not part of what kg_lambda scales: its slot is folded in, and cleared, here
         torch.add(self.out[kind], self.loss[self.ALIGN_SLOT], out=self.total[kind])
         self.loss[self.ALIGN_SLOT:self.ALIGN_SLOT + 1].zero_()
+        if self._acc_on:                                                # take_sums: the whole step's loss, alignment term included
+            self.acc[kind].add_(self.total[kind])
         return self.total[kind]
 
     # ------------------------------------------------------------------------------------------------ steps
