@@ -56,7 +56,10 @@ const char* ktup_last_error(void);
  *   "deterministic" [KTUP_DETERMINISTIC, 0]  1: ktup_train_rec_step / ktup_train_kg_step (gradients by atomics) run on ONE
  *                                        workgroup, so every gradient cell receives its adds from one wave in program order
  *                                        and two runs of a step give the same bits (sums of float atomics issued by several
- *                                        workgroups depend on the order they land in).  For parity runs: ~50x slower.        */
+ *                                        workgroups depend on the order they land in).  For parity runs: ~50x slower.
+ *   "eval_wide_topn" [KTUP_EVAL_WIDE_TOPN, -1]  read by the callers, not by the library: whether a model's evaluation pass at
+ *                                        17 <= topn <= 64 takes ktup_eval_dot_topk_wide / ktup_eval_cfkg_topk_wide -- 0: never (the
+ *                                        per-batch calls stay), 1: always, -1: where the caller's measured default says so          */
 int ktup_set_option(const char* name, int value);
 int ktup_get_option(const char* name, int* value);
 
@@ -904,6 +907,18 @@ int ktup_eval_dot_topk(const float* U, int64_t ldu, const float* I, int64_t ldi,
                        int64_t n_items, const float* user_add, const float* item_add, const int64_t* filt_off,
                        const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids, float* top_scores, void* ws,
                        void* stream);
+/* ------------------------------------------------------------------ the same pass for cut-offs up to 64
+ * ktup_eval_dot_topk with every argument, rule, score bit and list order unchanged, for 1 <= topn <= 64 (65: KTUP_ERR_UNSUPPORTED,
+ * workspace size 0).  A user's list is kept as two (topn <= 32) or four 16-key segments instead of one key per lane of a 16-lane
+ * row, merged by a longer network and at more LDS per workgroup; values at or below 16 are accepted so that the two list forms can be
+ * compared.  The split rule is the same 512 / topn, at most 32: 25 splits at topn 20, 8 at 64.  `ws`:
+ * ktup_eval_dot_topk_wide_workspace_bytes bytes.  The sweeps of TUP / KTUP (ktup_eval_pref_topk, ktup_eval_pref_topk_hard) keep
+ * lists of their own and decline above 16.                                                                                      */
+size_t ktup_eval_dot_topk_wide_workspace_bytes(int d, int64_t nq, int64_t n_items, int topn, int nsplit);
+int ktup_eval_dot_topk_wide(const float* U, int64_t ldu, const float* I, int64_t ldi, int d, const int64_t* u_ids, int64_t nq,
+                            int64_t n_items, const float* user_add, const float* item_add, const int64_t* filt_off,
+                            const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids, float* top_scores, void* ws,
+                            void* stream);
 
 /* =================================================================== training step of the inner-product recommenders
  * (csrc/ktup_dot_step.hip)  The rec step of FM (fm.py:58-67), coFM (cofm.py:99-108) and CKE (CKE.py:122-135) -- and of BPRMF, which
@@ -1002,6 +1017,14 @@ int ktup_eval_cfkg_topk(const float* U, int64_t ldu, const float* R, int64_t ldr
                         int64_t n_ent, const int64_t* cand_ids, int64_t n_cand, int d, const int64_t* u_ids, int64_t nq, int l1,
                         const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids,
                         float* top_scores, void* ws, void* stream);
+/* The same pass for 1 <= topn <= 64 on lists of two or four 16-key segments (see ktup_eval_dot_topk_wide): every argument, rule and
+ * score bit of ktup_eval_cfkg_topk; 65 is KTUP_ERR_UNSUPPORTED and workspace size 0.  `ws`: ktup_eval_cfkg_topk_wide_workspace_bytes
+ * bytes for the same arguments.                                                                                                  */
+size_t ktup_eval_cfkg_topk_wide_workspace_bytes(int d, int64_t nq, int64_t n_cand, int topn, int nsplit);
+int ktup_eval_cfkg_topk_wide(const float* U, int64_t ldu, const float* R, int64_t ldr, int64_t rel, const float* E, int64_t lde,
+                             int64_t n_ent, const int64_t* cand_ids, int64_t n_cand, int d, const int64_t* u_ids, int64_t nq, int l1,
+                             const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids,
+                             float* top_scores, void* ws, void* stream);
 
 /* =================================================================== the TransR training step in one launch (csrc/ktup_transr_step.hip)
  * transR.py:65-78 + utils/misc.py:21-26 scored, and knowledge_representation.py:176-204's step built, for the KG driver and CKE.

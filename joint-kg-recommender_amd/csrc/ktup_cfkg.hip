@@ -173,8 +173,9 @@ struct CfkgPassArgs {
 
 // What cfkg_pass_kernel adds to the sweep.  The sweep ranks s = -distance descending, like the inner-product pass: ascending
 // distance, ties -> lower j.
-template <int KS, bool L1>
+template <int KS, bool L1, int STC = 0>
 struct CfkgScorer {
+  using G = SweepGeom<KS, STC>;
   static constexpr int CROW4 = KS | 1;                                    // L1: float4 pitch of a query row in LDS
   static constexpr size_t CW = L1 ? (size_t)16 * CROW4 * 16 : 0;          // L1: a wave's 16 query rows
   static constexpr size_t LDS = 4 * CW;
@@ -207,7 +208,7 @@ struct CfkgScorer {
   KTUP_DEV v4 spare(int64_t c, bool live) const { return (v4){a.enorm ? a.enorm[c] : 0.f, live ? 1.f : 0.f, 0.f, 0.f}; }
   // acc: c.e on the matrix cores (squared L2), or the distance itself on the VALU against the same stage (L1): every lane owns the
   // 4 users x 16-candidate-tile slots the MFMA would have given it
-  KTUP_DEV void tile_math(const float (&av)[KS], const v4* eb, int kq, v4 (&acc)[SweepGeom<KS>::NSUB]) const {
+  KTUP_DEV void tile_math(const float (&av)[KS], const v4* eb, int kq, v4 (&acc)[G::NSUB]) const {
     if constexpr (L1) {
 #pragma unroll 2
       for (int s = 0; s < KS; ++s) {
@@ -215,8 +216,8 @@ struct CfkgScorer {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) cq[reg] = cw[reg * CROW4 + s];
 #pragma unroll
-        for (int t = 0; t < SweepGeom<KS>::NSUB; ++t) {
-          const v4 e = eb[t * 16 * SweepGeom<KS>::ROW4 + s];
+        for (int t = 0; t < G::NSUB; ++t) {
+          const v4 e = eb[t * 16 * G::ROW4 + s];
 #pragma unroll
           for (int reg = 0; reg < 4; ++reg) {
             const v4 z = cq[reg] - e;
@@ -242,25 +243,40 @@ __global__ __launch_bounds__(256, 2) void cfkg_pass_kernel(CfkgPassArgs a) {
   sweep_pass<KS, VEC>(a.sw, sc, smem);
 }
 
-template <int KS, bool L1>
+// the wide lists (ktup_topn.h) of ktup_eval_cfkg_topk_wide: two or four 16-key segments per user; two workgroups per CU only at the
+// narrowest rows.  L1 beyond d = 192 holds 65 KB of query rows beside 65 KB of stages, which leaves 24 KB:
+// the narrow lists' size.  There a stage is ONE 16-candidate tile (33 KB of stages), and the wide lists fit.
+constexpr int cfkg_wide_stage(int ks, bool l1) { return l1 && ks > 48 ? 16 : 0; }
+
+template <int KS, bool L1, int SEG>
+constexpr size_t cfkg_wide_lds() {
+  return SweepGeom<KS, cfkg_wide_stage(KS, L1)>::lds(CfkgScorer<KS, L1, cfkg_wide_stage(KS, L1)>::LDS, SEG);
+}
+
+template <int KS, bool VEC, bool L1, int SEG>
+__global__ __launch_bounds__(256, sweep_wide_wgs(cfkg_wide_lds<KS, L1, SEG>())) void cfkg_pass_wide_kernel(CfkgPassArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int STC = cfkg_wide_stage(KS, L1);
+  CfkgScorer<KS, L1, STC> sc{a};
+  sweep_pass<KS, VEC, SEG, STC>(a.sw, sc, smem);
+}
+
+template <int KS, bool L1, int SEG>
 int launch_cfkg_pass(const CfkgPassArgs& a, hipStream_t st, const char* name) {
-  constexpr size_t lds = SweepGeom<KS>::lds(CfkgScorer<KS, L1>::LDS);
-  return a.sw.vec ? sweep_launch<lds>(cfkg_pass_kernel<KS, true, L1>, a, a.sw, st, name) : sweep_launch<lds>(cfkg_pass_kernel<KS, false, L1>, a, a.sw, st, name);
+  constexpr int STC = SEG == 1 ? 0 : cfkg_wide_stage(KS, L1);
+  constexpr size_t lds = SweepGeom<KS, STC>::lds(CfkgScorer<KS, L1, STC>::LDS, SEG);
+  if constexpr (SEG == 1)
+    return a.sw.vec ? sweep_launch<lds>(cfkg_pass_kernel<KS, true, L1>, a, a.sw, st, name) : sweep_launch<lds>(cfkg_pass_kernel<KS, false, L1>, a, a.sw, st, name);
+  else
+    return a.sw.vec ? sweep_launch<lds>(cfkg_pass_wide_kernel<KS, true, L1, SEG>, a, a.sw, st, name)
+                    : sweep_launch<lds>(cfkg_pass_wide_kernel<KS, false, L1, SEG>, a, a.sw, st, name);
 }
 
-}  // namespace
-}  // namespace ktup
-
-extern "C" size_t ktup_eval_cfkg_topk_workspace_bytes(int d, int64_t nq, int64_t n_cand, int topn, int nsplit) {
-  (void)d;
-  return sweep_workspace_bytes(nq, n_cand, topn, nsplit, 1);
-}
-
-extern "C" int ktup_eval_cfkg_topk(const float* U, int64_t ldu, const float* R, int64_t ldr, int64_t rel, const float* E, int64_t lde,
-                                   int64_t n_ent, const int64_t* cand_ids, int64_t n_cand, int d, const int64_t* u_ids, int64_t nq, int l1,
-                                   const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids,
-                                   float* top_scores, void* ws, void* stream) {
-  const char* name = "ktup_eval_cfkg_topk";
+// both entry points; topn_max: TOPN_MAX (narrow lists) or TOPN_WIDE_MAX (wide lists, at every topn)
+int cfkg_topk(const char* name, int topn_max, const float* U, int64_t ldu, const float* R, int64_t ldr, int64_t rel, const float* E, int64_t lde,
+              int64_t n_ent, const int64_t* cand_ids, int64_t n_cand, int d, const int64_t* u_ids, int64_t nq, int l1,
+              const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids, float* top_scores, void* ws,
+              void* stream) {
   KTUP_REQUIRE(U && R && E && u_ids && top_ids && ws, "%s: null table, id, output or workspace pointer", name);
   KTUP_REQUIRE(d >= 1 && nq >= 0 && n_ent > 0 && n_cand > 0 && topn > 0 && nsplit >= 0,
                "%s: bad sizes (embedding_size %d, %lld users, %lld entities, %lld candidates, topn %d, nsplit %d)", name, d, (long long)nq,
@@ -271,7 +287,7 @@ extern "C" int ktup_eval_cfkg_topk(const float* U, int64_t ldu, const float* R, 
                (long long)n_ent, (long long)n_cand);
   KTUP_REQUIRE((filt_off == nullptr) == (filt_ids == nullptr), "%s: filt_off and filt_ids go together", name);
   KTUP_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: the workspace must be 16-byte aligned", name);
-  if (topn > TOPN_MAX) return set_error(KTUP_ERR_UNSUPPORTED, "%s: topn %d > %d", name, topn, TOPN_MAX);
+  if (topn > topn_max) return set_error(KTUP_ERR_UNSUPPORTED, "%s: topn %d > %d", name, topn, topn_max);
   if (d > 256) return set_error(KTUP_ERR_UNSUPPORTED, "%s: embedding_size %d > 256", name, d);
   if (n_cand >= ((int64_t)1 << 31)) return set_error(KTUP_ERR_UNSUPPORTED, "%s: %lld candidates do not fit 32-bit ids", name, (long long)n_cand);
   if (nq == 0) return KTUP_OK;
@@ -288,9 +304,43 @@ extern "C" int ktup_eval_cfkg_topk(const float* U, int64_t ldu, const float* R, 
     if (int rc = check_launch(name)) return rc;
     a.enorm = en;
   }
+  const int seg = topn_max == TOPN_MAX ? 1 : sweep_segments(topn);
   const int rc = with_k_steps(d, [&](auto ks) {
     constexpr int KS = decltype(ks)::value;
-    return l1 ? launch_cfkg_pass<KS, true>(a, st, name) : launch_cfkg_pass<KS, false>(a, st, name);
+    auto go = [&](auto sg) {
+      constexpr int SEG = decltype(sg)::value;
+      return l1 ? launch_cfkg_pass<KS, true, SEG>(a, st, name) : launch_cfkg_pass<KS, false, SEG>(a, st, name);
+    };
+    return seg == 1 ? go(std::integral_constant<int, 1>{}) : seg == 2 ? go(std::integral_constant<int, 2>{}) : go(std::integral_constant<int, 4>{});
   });
   return rc ? rc : sweep_merge<false>(a.sw, top_ids, top_scores, st, name);
+}
+
+}  // namespace
+}  // namespace ktup
+
+extern "C" size_t ktup_eval_cfkg_topk_workspace_bytes(int d, int64_t nq, int64_t n_cand, int topn, int nsplit) {
+  (void)d;
+  return sweep_workspace_bytes(nq, n_cand, topn, TOPN_MAX, nsplit, 1);
+}
+
+extern "C" int ktup_eval_cfkg_topk(const float* U, int64_t ldu, const float* R, int64_t ldr, int64_t rel, const float* E, int64_t lde,
+                                   int64_t n_ent, const int64_t* cand_ids, int64_t n_cand, int d, const int64_t* u_ids, int64_t nq, int l1,
+                                   const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids,
+                                   float* top_scores, void* ws, void* stream) {
+  return cfkg_topk("ktup_eval_cfkg_topk", TOPN_MAX, U, ldu, R, ldr, rel, E, lde, n_ent, cand_ids, n_cand, d, u_ids, nq, l1, filt_off, filt_ids,
+                   topn, nsplit, top_ids, top_scores, ws, stream);
+}
+
+extern "C" size_t ktup_eval_cfkg_topk_wide_workspace_bytes(int d, int64_t nq, int64_t n_cand, int topn, int nsplit) {
+  (void)d;
+  return sweep_workspace_bytes(nq, n_cand, topn, TOPN_WIDE_MAX, nsplit, 1);
+}
+
+extern "C" int ktup_eval_cfkg_topk_wide(const float* U, int64_t ldu, const float* R, int64_t ldr, int64_t rel, const float* E, int64_t lde,
+                                        int64_t n_ent, const int64_t* cand_ids, int64_t n_cand, int d, const int64_t* u_ids, int64_t nq,
+                                        int l1, const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids,
+                                        float* top_scores, void* ws, void* stream) {
+  return cfkg_topk("ktup_eval_cfkg_topk_wide", TOPN_WIDE_MAX, U, ldu, R, ldr, rel, E, lde, n_ent, cand_ids, n_cand, d, u_ids, nq, l1, filt_off,
+                   filt_ids, topn, nsplit, top_ids, top_scores, ws, stream);
 }

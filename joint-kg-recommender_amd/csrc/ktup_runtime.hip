@@ -65,6 +65,8 @@ Option g_opts[] = {
                                                                             // (ktup_get_option; ops.eval_kg_ranks_transd), who otherwise take ktup_eval_kg_ranks_transd_fused: the same ranks
     {"transr_fused", "KTUP_TRANSR_FUSED", {env_int("KTUP_TRANSR_FUSED", 1)}},         // 0: the TransR / CKE link-prediction pass keeps the chunked score-matrix route; read by the callers
                                                                             // (ops.eval_kg_ranks_transr), who otherwise take ktup_eval_kg_ranks_transr_fused where it is the default: the same ranks
+    {"eval_wide_topn", "KTUP_EVAL_WIDE_TOPN", {env_int("KTUP_EVAL_WIDE_TOPN", -1)}},   // rec evaluation at 17 <= topn <= 64, read by the callers (ops.topk_sweep_for): 0: the batch walk stays, 1: the wide-list
+                                                                            // sweep (ktup_eval_dot_topk_wide, ktup_eval_cfkg_topk_wide), -1: the sweep where the caller's measured default says so
 };
 Option* find(const char* name) {
   for (auto& o : g_opts)

@@ -11,6 +11,15 @@
 //     decide equality, NaNs and a list that is still short) and its bit in the pass's filter bitmap (built once per pass from the CSR
 //     lists, read from L2 by candidates only) is clear;
 //   * the splits' partial lists are merged by a last, tiny launch (topk_merge_kernel, ktup_topn.h).
+// The list has two widths (ktup_topn.h): SEG = 1, one key per lane of the user's 16-lane row (topn <= 16), is what the narrow entry
+// points launch; SEG = 2 and 4 (topn <= 32, <= 64) are the wide entry points' (ktup_eval_dot_topk_wide, ktup_eval_cfkg_topk_wide).
+// A wide list costs 2 or 6 KB more LDS per wave and a longer merge network; scorers, stages, filter bits, pending rows and the
+// append are the same code, so a score is the same bits at every width.  The sweeps of TUP / KTUP (ktup_eval_pass.hip,
+// ktup_eval.hip) have list code of their own and stay at 16.  Measured against the batch walk, which was all there was above 16
+// (profiles/wide_topn_times.txt, whole pass through the driver): inner products 6040 x 3240, d = 64: topn 20 0.85 -> 0.25 ms, topn 50
+// 1.52 -> 0.49 ms; 512 x 100,000: 1.65 -> 0.46 and 3.40 -> 1.05 ms; CFKG at d = 100: 1.31 -> 0.84 (L1) and 1.19 -> 0.65 ms (squared
+// L2) at topn 20.  The registers of a wide kernel are bounded for the workgroups per CU its LDS admits (sweep_wide_wgs); no wide
+// instantiation spills.
 // Here live, ONCE: the geometry, the pass body (sweep_pass), the split rule, the workspace layout, the filter bitmap, the launch
 // ladder over the row width and the merge launch.  What a model adds is its SCORER, a small type that supplies
 //     static constexpr size_t LDS                       bytes of its own between the stages and the waves' lists (a multiple of 16)
@@ -42,7 +51,13 @@ namespace {
 
 constexpr int NSPLIT_MAX = 32;   // candidate splits: NSPLIT_MAX * TOPN_MAX keys per user is what the merge holds, eight per lane
 constexpr int MERGE_PER_LANE = NSPLIT_MAX * TOPN_MAX / 64;
-constexpr size_t WAVE_LDS = (size_t)16 * PCAP * 8 + (size_t)16 * 16 * 8;   // pending rows | lists
+// the split rule: 512 / topn splits, at most 32 -- 32 up to topn 16, 25 at 20, 10 at 50, 8 at 64
+constexpr int sweep_max_splits(int topn) { return 64 * MERGE_PER_LANE / topn < NSPLIT_MAX ? 64 * MERGE_PER_LANE / topn : NSPLIT_MAX; }
+constexpr size_t wave_lds(int seg) { return (size_t)16 * PCAP * 8 + (size_t)16 * 16 * seg * 8; }   // pending rows | lists of seg 16-key segments
+constexpr int sweep_segments(int topn) { return topn <= 32 ? 2 : 4; }   // the wide entry points' list width
+constexpr size_t SWEEP_LDS_MAX = 160 * 1024;
+// the workgroups per CU a wide kernel's registers are bounded for: two where two fit the LDS, else one (and 512 registers a lane)
+constexpr int sweep_wide_wgs(size_t lds) { return 2 * lds <= SWEEP_LDS_MAX ? 2 : 1; }
 
 struct SweepArgs {
   const int64_t* u_ids; int64_t nq, n;  // the users' rows; users and candidates of the pass
@@ -54,9 +69,10 @@ struct SweepArgs {
 
 // KS: 4-wide k steps (d <= 4 KS; the padding holds zeros on both sides: fma(0, 0, acc) = acc, a chain that starts at +0 never holds
 // -0, and it adds nothing to a distance)
-template <int KS>
+// STC: candidates per stage where a kernel cannot afford the usual ones (0: 64, or 32 for the wide rows)
+template <int KS, int STC = 0>
 struct SweepGeom {
-  static constexpr int ST = KS > 32 ? 32 : 64;       // candidates per stage
+  static constexpr int ST = STC ? STC : KS > 32 ? 32 : 64;   // candidates per stage
   static constexpr int NSUB = ST / 16;               // 16-candidate tiles per stage = accumulators per wave
   static constexpr int CPR = KS + 1;                 // float4 slots per row: KS operand quads + the spare slot
   static constexpr int ROW4 = CPR | 1;               // the row's float4 pitch in LDS: odd
@@ -64,27 +80,27 @@ struct SweepGeom {
   static constexpr int SLOTS = ST * KS;              // operand quads a stage loads
   static constexpr int NPRE = (SLOTS + 255) / 256;   // float4 per thread in flight for the next stage
   static constexpr size_t STAGES = (size_t)2 * STG * 16;
-  static constexpr size_t lds(size_t scorer) { return STAGES + scorer + 4 * WAVE_LDS; }   // stages | the scorer's | pending rows and lists
+  static constexpr size_t lds(size_t scorer, int seg = 1) { return STAGES + scorer + 4 * wave_lds(seg); }   // stages | the scorer's | pending rows and lists
 };
 
 // ---- device side -----------------------------------------------------------------------------
-// The pass of one workgroup (256 threads, SweepGeom<KS>::lds(S::LDS) bytes at smem).
-template <int KS, bool VEC, class S>
+// The pass of one workgroup (256 threads, SweepGeom<KS, STC>::lds(S::LDS, SEG) bytes at smem); SEG: 16-key segments of a user's list.
+template <int KS, bool VEC, int SEG = 1, int STC = 0, class S>
 KTUP_DEV void sweep_pass(const SweepArgs& a, S& sc, char* smem) {
-  using G = SweepGeom<KS>;
+  using G = SweepGeom<KS, STC>;
   constexpr int ST = G::ST, NSUB = G::NSUB, ROW4 = G::ROW4, STG = G::STG, SLOTS = G::SLOTS, NPRE = G::NPRE;
   v4* Xb = reinterpret_cast<v4*>(smem);                                   // [2][STG] candidate stages
   const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4, j = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  uint64_t* pbuf = reinterpret_cast<uint64_t*>(smem + G::STAGES + S::LDS + (size_t)w * WAVE_LDS);   // [16][PCAP] pending candidates
-  uint64_t* tk = pbuf + 16 * PCAP;                                        // [16][16] the users' sorted lists (touched by merges only)
+  uint64_t* pbuf = reinterpret_cast<uint64_t*>(smem + G::STAGES + S::LDS + (size_t)w * wave_lds(SEG));   // [16][PCAP] pending candidates
+  uint64_t* tk = pbuf + 16 * PCAP;                                        // [16][SEG][16] the users' sorted lists (touched by merges only)
   const int64_t ub = (int64_t)(blockIdx.x / (unsigned)a.nsplit);
   const int sp = (int)(blockIdx.x - (unsigned)ub * (unsigned)a.nsplit);
   const int64_t u0 = ub * 64 + 16 * w;
   const int64_t i_lo = (int64_t)sp * a.split;
   const int64_t i_hi = min(a.n, i_lo + a.split);
   const int topn = a.topn, d = a.d;
-  for (int idx = lane; idx < 16 * 16; idx += 64) tk[idx] = PKEY_MAX;
+  for (int idx = lane; idx < 16 * 16 * SEG; idx += 64) tk[idx] = PKEY_MAX;
   // A operands of the whole pass: lane (kq, j) holds element 4 s + kq of user j's query row for every k step s
   float av[KS];
   {
@@ -165,11 +181,27 @@ KTUP_DEV void sweep_pass(const SweepArgs& a, S& sc, char* smem) {
       if (!__builtin_amdgcn_ballot_w64(all ? n > 0 : n >= 16)) continue;
       const int ur = 4 * kq + reg;
       const uint64_t* row = pbuf + ur * PCAP;
-      const uint64_t merged = row_merge_pending(tk[ur * 16 + j], row, n, topn, j);   // all four rows of the slot at once
-      tk[ur * 16 + j] = merged;
+      uint64_t merged;                                                                // the segment that holds the n-th key
+      if constexpr (SEG == 1) {
+        merged = row_merge_pending(tk[ur * 16 + j], row, n, topn, j);                 // all four rows of the slot at once
+        tk[ur * 16 + j] = merged;
+      } else {
+        uint64_t* lst = tk + ur * 16 * SEG + j;
+        uint64_t seg[SEG];
+#pragma unroll
+        for (int s = 0; s < SEG; ++s) seg[s] = lst[16 * s];
+        row_merge_pending_wide<SEG>(seg, row, n, topn, j);
+        merged = seg[0];
+#pragma unroll
+        for (int s = 0; s < SEG; ++s) {
+          lst[16 * s] = seg[s];
+          if (s == (topn - 1) >> 4) merged = seg[s];
+        }
+      }
       pend[reg] = 0;
-      const uint32_t nhi = (uint32_t)__shfl((int)(uint32_t)(merged >> 32), rowbase + topn - 1, 64);
-      const uint32_t nlo = (uint32_t)__shfl((int)(uint32_t)merged, rowbase + topn - 1, 64);
+      const int nth = SEG == 1 ? rowbase + topn - 1 : rowbase + ((topn - 1) & 15);
+      const uint32_t nhi = (uint32_t)__shfl((int)(uint32_t)(merged >> 32), nth, 64);
+      const uint32_t nlo = (uint32_t)__shfl((int)(uint32_t)merged, nth, 64);
       if (in[reg]) {                                                                  // (rows past the end keep 0 / +inf)
         thr[reg] = ((uint64_t)nhi << 32) | nlo;
         thrf[reg] = -topn_key_score(nhi);                                               // negated back (NaN: list short)
@@ -228,11 +260,24 @@ KTUP_DEV void sweep_pass(const SweepArgs& a, S& sc, char* smem) {
     __syncthreads();
   }
   flush(true);
-  if (j < topn) {
+  if constexpr (SEG == 1) {                                                // (the loop below with SEG = 1, as it was written for the narrow
+    if (j < topn) {                                                        //  lists alone: through the loop the same stores come out of
+#pragma unroll                                                             //  another register allocation)
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t ur = u0 + 4 * kq + reg;
+        if (ur < a.nq) a.part[(ur * a.nsplit + sp) * topn + j] = tk[(4 * kq + reg) * 16 + j];
+      }
+    }
+  } else {
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int64_t ur = u0 + 4 * kq + reg;
-      if (ur < a.nq) a.part[(ur * a.nsplit + sp) * topn + j] = tk[(4 * kq + reg) * 16 + j];
+    for (int s = 0; s < SEG; ++s) {
+      const int p = 16 * s + j;                                            // this lane's key of segment s
+      if (p >= topn) continue;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t ur = u0 + 4 * kq + reg;
+        if (ur < a.nq) a.part[(ur * a.nsplit + sp) * topn + p] = tk[(4 * kq + reg) * 16 * SEG + p];
+      }
     }
   }
 }
@@ -256,10 +301,12 @@ KTUP_DEV void sweep_tile_dot(const float (&av)[KS], const v4* eb, int kq, v4 (&a
 // list of its own per user, so more splits mean more candidates through the append / merge path and a prologue each; fewer leave CUs
 // idle.  Measured (one MI355X, inner products, d = 64, topn 10, ~165 filtered ids per user, whole call): 6040 x 3240: 4 splits 143 us
 // (1: 260, 8: 165, 12: 189); 512 x 100,000: 32 splits 279 us (16: 431, 8: 710); 30,000 x 25,000: 1 split 1.76 ms (3: 2.09, 8: 2.50).
-inline int sweep_nsplit(int64_t nq, int64_t n, int want, int64_t* split) {
+// At most sweep_max_splits(topn): what the merge kernel holds.
+inline int sweep_nsplit(int64_t nq, int64_t n, int topn, int want, int64_t* split) {
   const int64_t nub = (nq + 63) / 64;
+  const int64_t cap = sweep_max_splits(topn);
   int64_t ns = want > 0 ? want : (320 + nub - 1) / (nub > 0 ? nub : 1);
-  ns = ns < 1 ? 1 : ns > NSPLIT_MAX ? NSPLIT_MAX : ns;
+  ns = ns < 1 ? 1 : ns > cap ? cap : ns;
   int64_t si = (n + ns - 1) / ns;
   si = (si + 15) / 16 * 16;
   if (want <= 0 && si < 256) si = 256;                                     // (a workgroup's prologue wants some candidates to pay for it)
@@ -268,11 +315,11 @@ inline int sweep_nsplit(int64_t nq, int64_t n, int want, int64_t* split) {
 }
 
 // workspace: the partial lists (8-byte entries, so the bits start on an 8-byte boundary) | the filter bits | cand_floats floats per
-// candidate.  0 for sizes no pass runs with.
-inline size_t sweep_workspace_bytes(int64_t nq, int64_t n, int topn, int nsplit, int cand_floats) {
-  if (nq <= 0 || n <= 0 || topn <= 0 || topn > TOPN_MAX || nsplit < 0) return 0;
+// candidate.  0 for sizes no pass runs with (topn_max: TOPN_MAX, or TOPN_WIDE_MAX for the wide entry points).
+inline size_t sweep_workspace_bytes(int64_t nq, int64_t n, int topn, int topn_max, int nsplit, int cand_floats) {
+  if (nq <= 0 || n <= 0 || topn <= 0 || topn > topn_max || nsplit < 0) return 0;
   int64_t si = 0;
-  const int ns = sweep_nsplit(nq, n, nsplit, &si);
+  const int ns = sweep_nsplit(nq, n, topn, nsplit, &si);
   const size_t part = (size_t)nq * ns * topn * sizeof(uint64_t);
   const size_t bits = (size_t)nq * (size_t)((n + 31) / 32) * sizeof(uint32_t);
   return part + bits + (size_t)cand_floats * n * sizeof(float) + 16;
@@ -282,7 +329,7 @@ inline size_t sweep_workspace_bytes(int64_t nq, int64_t n, int topn, int nsplit,
 // *cand_floats (optional): the per-candidate floats of the workspace.
 inline int sweep_prepare(SweepArgs& a, int nsplit, const int64_t* filt_off, const int32_t* filt_ids, void* ws, float** cand_floats,
                          hipStream_t st, const char* name) {
-  a.nsplit = sweep_nsplit(a.nq, a.n, nsplit, &a.split);
+  a.nsplit = sweep_nsplit(a.nq, a.n, a.topn, nsplit, &a.split);
   a.part = reinterpret_cast<uint64_t*>(ws);
   a.bm = nullptr;
   a.bm_words = (a.n + 31) / 32;
@@ -313,7 +360,7 @@ inline int with_k_steps(int d, F f) {
 // one workgroup per (64 users, split)
 template <size_t LDS, class Args>
 int sweep_launch(void (*kernel)(Args), const Args& args, const SweepArgs& a, hipStream_t st, const char* name) {
-  static_assert(LDS <= 160 * 1024, "the stages, what the scorer holds and the lists fit the LDS");
+  static_assert(LDS <= SWEEP_LDS_MAX, "the stages, what the scorer holds and the lists fit the LDS");
   (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
   hipLaunchKernelGGL(kernel, dim3((unsigned)((a.nq + 63) / 64 * a.nsplit)), dim3(256), LDS, st, args);
   return check_launch(name);

@@ -4,6 +4,9 @@
 // so the order is total: ascending score, ties -> lower id first.  A one-sweep pass keeps a user's sorted top-n list (one key per
 // lane of a 16-lane row) in LDS and touches it only when 16 candidates are pending for it; the catalogue splits' partial lists
 // are merged by topk_merge_kernel.  How a sweep keeps and renews its thresholds is its own business.
+// Two list widths: the NARROW list above (topn <= TOPN_MAX = 16; every sweep), and the WIDE list of SEG = 2 or 4 such 16-key
+// segments (topn <= 16 SEG <= TOPN_WIDE_MAX = 64; ktup_sweep_pass.h only): element p of a user's list is key (p >> 4) of lane
+// p & 15, so a lane holds SEG keys.  Pending buffer, append and merge kernel are the same for both.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +19,7 @@ namespace {
 
 constexpr uint64_t PKEY_MAX = ~0ull;   // "no key": above every real one
 constexpr int TOPN_MAX = 16;           // top-n list capacity per user: one element per lane of a 16-lane row
+constexpr int TOPN_WIDE_MAX = 64;      // ... of a wide list: four 16-key segments, four keys per lane
 constexpr int PCAP = 32;               // pending candidates per user between two merges (a merge is due at 16; one tile adds at most 16)
 
 // `descending` negates the score first, exactly like `per_scores = -pred` (utils/misc.py:93,180).
@@ -75,6 +79,46 @@ KTUP_DEV uint64_t row_merge_pending(uint64_t list, const uint64_t* row, int n, i
   uint64_t merged = row_merge16(list, j < n ? row[j] : PKEY_MAX, j);
   if (__builtin_amdgcn_ballot_w64(n > 16)) merged = row_merge16(j < topn ? merged : PKEY_MAX, 16 + j < n ? row[16 + j] : PKEY_MAX, j);
   return j < topn ? merged : PKEY_MAX;
+}
+// The wide list: list[s] is this lane's key of segment s, the 16 SEG keys ascending in p = 16 s + j.  Against the ascending
+// candidates C the list's LAST segment takes min(L[16 (SEG - 1) + j], C[15 - j]): with C padded by "no key" to the list's length that
+// is the half-cleaner of a bitonic merge, so the 16 SEG keys now held are the smallest of the 16 SEG + 16 and form a bitonic sequence
+// (ascending segments, then a last one that rises and falls, or only falls if even its first key gave way).  The bitonic merge of
+// that sequence: strides 32 and 16 exchange between the lane's own keys, strides 8 to 1 are the row network on every segment.  A
+// round is 10 + 4 SEG row exchanges and SEG / 2 * log2(SEG) in-lane ones: 18 + 1 with two segments, 26 + 4 with four (narrow: 14).
+template <int SEG>
+KTUP_DEV void row_merge16_wide(uint64_t (&list)[SEG], uint64_t cand, int j) {
+  static_assert(SEG == 2 || SEG == 4, "a wide list is two or four 16-key segments");
+  const bool b1 = (j & 1) == 0, b2 = (j & 2) == 0, b4 = (j & 4) == 0, b8 = (j & 8) == 0;
+  row_cmpx<1>(cand, b1 == b2);                                            // the candidates' sort: row_merge16's 10 exchanges
+  row_cmpx<2>(cand, b2 == b4); row_cmpx<1>(cand, b1 == b4);
+  row_cmpx<4>(cand, b4 == b8); row_cmpx<2>(cand, b2 == b8); row_cmpx<1>(cand, b1 == b8);
+  row_cmpx<8>(cand, b8); row_cmpx<4>(cand, b4); row_cmpx<2>(cand, b2); row_cmpx<1>(cand, b1);
+  const uint64_t r = row_mirror64(cand);
+  if (r < list[SEG - 1]) list[SEG - 1] = r;
+#pragma unroll
+  for (int h = SEG / 2; h >= 1; h >>= 1) {
+#pragma unroll
+    for (int s = 0; s < SEG; ++s) {
+      if (s & h) continue;
+      const uint64_t lo = list[s], hi = list[s | h];
+      list[s] = hi < lo ? hi : lo;
+      list[s | h] = hi < lo ? lo : hi;
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < SEG; ++s) {
+    row_cmpx<8>(list[s], b8); row_cmpx<4>(list[s], b4); row_cmpx<2>(list[s], b2); row_cmpx<1>(list[s], b1);
+  }
+}
+// row_merge_pending for a wide list, in place (the first round's surplus keys are above every key the second round keeps: no cut
+// between the rounds)
+template <int SEG>
+KTUP_DEV void row_merge_pending_wide(uint64_t (&list)[SEG], const uint64_t* row, int n, int topn, int j) {
+  row_merge16_wide<SEG>(list, j < n ? row[j] : PKEY_MAX, j);
+  if (__builtin_amdgcn_ballot_w64(n > 16)) row_merge16_wide<SEG>(list, 16 + j < n ? row[16 + j] : PKEY_MAX, j);
+#pragma unroll
+  for (int s = 0; s < SEG; ++s) list[s] = 16 * s + j < topn ? list[s] : PKEY_MAX;
 }
 // Where the candidates of a ballot go in their rows' pending buffers: lane (kq, j) belongs to row kq of the wave's four 16-lane
 // rows.  No atomics: `pend`, the row's count, is replicated over its 16 lanes.

@@ -169,6 +169,8 @@ SIGNATURES = {
                                         c_p, c_p, c_l, c_l, c_p, c_p, c_p],
     'ktup_eval_dot_topk_workspace_bytes': [c_i, c_l, c_l, c_i, c_i],
     'ktup_eval_dot_topk': [c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
+    'ktup_eval_dot_topk_wide_workspace_bytes': [c_i, c_l, c_l, c_i, c_i],
+    'ktup_eval_dot_topk_wide': [c_p, c_l, c_p, c_l, c_i, c_p, c_l, c_l, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
     'ktup_train_dot_step_supported': [c_i],
     'ktup_train_dot_step': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_p, c_i, c_p, c_p, c_l, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p],
     'ktup_reg_align_pairs': [c_p, c_l, c_p, c_l, c_i, c_p, c_p, c_p, c_l, c_l, c_i, c_f, c_p, c_p, c_p, c_p],
@@ -176,6 +178,8 @@ SIGNATURES = {
     'ktup_train_cfkg_rec_step': [c_p, c_l, c_p, c_l, c_p, c_l, c_l, c_i, c_p, c_p, c_l, c_i, c_f, c_f, c_p, c_p, c_p, c_p, c_p],
     'ktup_eval_cfkg_topk_workspace_bytes': [c_i, c_l, c_l, c_i, c_i],
     'ktup_eval_cfkg_topk': [c_p, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
+    'ktup_eval_cfkg_topk_wide_workspace_bytes': [c_i, c_l, c_l, c_i, c_i],
+    'ktup_eval_cfkg_topk_wide': [c_p, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
     'ktup_eval_kg_ranks_transr_fused_supported': [c_i, c_i, c_l],
     'ktup_eval_kg_ranks_transr_fused_workspace_bytes': [c_i, c_l, c_l, c_l, c_l, c_i],
     'ktup_eval_kg_ranks_transr_fused': [c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_l,
@@ -195,7 +199,8 @@ _RESTYPE = {'ktup_last_error': ctypes.c_char_p, 'ktup_shard_reduce_list_len': ct
             'ktup_score_kg_bwd_workspace_bytes': ctypes.c_size_t, 'ktup_score_bprmf_bwd_workspace_bytes': ctypes.c_size_t,
             'ktup_train_rec_step_rows_ws_bytes': ctypes.c_size_t, 'ktup_eval_transd_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_kg_ranks_transd_workspace_bytes': ctypes.c_size_t, 'ktup_eval_dot_topk_workspace_bytes': ctypes.c_size_t,
-            'ktup_eval_cfkg_topk_workspace_bytes': ctypes.c_size_t,
+            'ktup_eval_cfkg_topk_workspace_bytes': ctypes.c_size_t, 'ktup_eval_dot_topk_wide_workspace_bytes': ctypes.c_size_t,
+            'ktup_eval_cfkg_topk_wide_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_kg_ranks_transd_fused_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_kg_ranks_transr_fused_workspace_bytes': ctypes.c_size_t,
             'ktup_feed_align_lists_workspace_bytes': ctypes.c_size_t}

@@ -906,6 +906,18 @@ def eval_dot_topk(U, I, u, topn, filt_off=None, filt_ids=None, user_add=None, it
     matrix; the bits and the order of eval_bprmf + the two adds + topk_filtered(descending=True).  user_add: (len(u),) fp32, item_add:
     (n_items,) fp32, either may be None.  -> int32 (len(u), topn) ids (-1 padded) [, scores], or None where the entry point declines
     the shape (topn > 16, d > 256): keep the per-batch calls."""
+    return _eval_dot_topk('ktup_eval_dot_topk', TOPN_MAX, U, I, u, topn, filt_off, filt_ids, user_add, item_add, with_scores, nsplit)
+
+
+@torch.no_grad()
+def eval_dot_topk_wide(U, I, u, topn, filt_off=None, filt_ids=None, user_add=None, item_add=None, with_scores=False, nsplit=0):
+    """eval_dot_topk on the wide lists (ktup_eval_dot_topk_wide): the same scores, order and arguments for 1 <= topn <= 64 (a user's
+    list is two or four 16-key segments; at most 512 / topn catalogue splits).  None for topn > 64 and d > 256."""
+    return _eval_dot_topk('ktup_eval_dot_topk_wide', TOPN_WIDE_MAX, U, I, u, topn, filt_off, filt_ids, user_add, item_add, with_scores,
+                          nsplit)
+
+
+def _eval_dot_topk(entry, topn_max, U, I, u, topn, filt_off, filt_ids, user_add, item_add, with_scores, nsplit):
     dev = _dev(_table('user table', U)); _table('item table', I)
     if I.device != dev or I.shape[1] != U.shape[1]:
         raise L.KtupError('user and item tables must share the device and the embedding size')
@@ -919,13 +931,13 @@ def eval_dot_topk(U, I, u, topn, filt_off=None, filt_ids=None, user_add=None, it
             raise L.KtupError('%s must be a 1-D fp32 tensor of %d entries on %s' % (name, n, dev))
         return t.detach().contiguous()
     user_add, item_add = _term('user_add', user_add, nq), _term('item_add', item_add, ni)
-    if not (0 < topn <= 16) or nq == 0 or ni == 0 or not (0 < d <= 256):
+    if not (0 < topn <= topn_max) or nq == 0 or ni == 0 or not (0 < d <= 256):
         return None
     filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
     args = (_p(U), U.stride(0), _p(I), I.stride(0), d, _p(u), nq, ni, _p(user_add), _p(item_add), _p(filt_off), _p(filt_ids), int(topn),
             int(nsplit))
-    return _topn_sweep('ktup_eval_dot_topk', args, L.load().ktup_eval_dot_topk_workspace_bytes(d, nq, ni, int(topn), int(nsplit)), nq, topn,
-                       dev, with_scores)
+    return _topn_sweep(entry, args, getattr(L.load(), entry + '_workspace_bytes')(d, nq, ni, int(topn), int(nsplit)), nq, topn, dev,
+                       with_scores)
 
 
 @torch.no_grad()
@@ -935,6 +947,18 @@ def eval_cfkg_topk(U, R, rel, E, u, topn, l1, cand_ids=None, filt_off=None, filt
     (users x candidates) matrix; the order of eval_transe + topk_filtered(descending=False), the scores up to fp32 rounding.  Filter
     ids and the returned ids are in j space.  -> int32 (len(u), topn) ids (-1 padded) [, scores], or None where the entry point
     declines the shape (topn > 16, d > 256): keep the per-batch calls."""
+    return _eval_cfkg_topk('ktup_eval_cfkg_topk', TOPN_MAX, U, R, rel, E, u, topn, l1, cand_ids, filt_off, filt_ids, with_scores, nsplit)
+
+
+@torch.no_grad()
+def eval_cfkg_topk_wide(U, R, rel, E, u, topn, l1, cand_ids=None, filt_off=None, filt_ids=None, with_scores=False, nsplit=0):
+    """eval_cfkg_topk on the wide lists (ktup_eval_cfkg_topk_wide): the same scores, order and arguments for 1 <= topn <= 64.  None
+    for topn > 64 and d > 256."""
+    return _eval_cfkg_topk('ktup_eval_cfkg_topk_wide', TOPN_WIDE_MAX, U, R, rel, E, u, topn, l1, cand_ids, filt_off, filt_ids, with_scores,
+                           nsplit)
+
+
+def _eval_cfkg_topk(entry, topn_max, U, R, rel, E, u, topn, l1, cand_ids, filt_off, filt_ids, with_scores, nsplit):
     dev = _dev(_table('user table', U)); _table('relation table', R); _table('entity table', E)
     if R.device != dev or E.device != dev or R.shape[1] != U.shape[1] or E.shape[1] != U.shape[1]:
         raise L.KtupError('user, relation and entity tables must share the device and the embedding size')
@@ -945,13 +969,35 @@ def eval_cfkg_topk(U, R, rel, E, u, topn, l1, cand_ids=None, filt_off=None, filt
         cand_ids = _ids('cand_ids', cand_ids, dev)
     nq, d, ne = u.numel(), U.shape[1], E.shape[0]
     nc = ne if cand_ids is None else cand_ids.numel()
-    if not (0 < topn <= 16) or nq == 0 or nc == 0 or not (0 < d <= 256):
+    if not (0 < topn <= topn_max) or nq == 0 or nc == 0 or not (0 < d <= 256):
         return None
     filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
     args = (_p(U), U.stride(0), _p(R), R.stride(0), int(rel), _p(E), E.stride(0), ne, _p(cand_ids), nc, d, _p(u), nq, int(bool(l1)),
             _p(filt_off), _p(filt_ids), int(topn), int(nsplit))
-    return _topn_sweep('ktup_eval_cfkg_topk', args, L.load().ktup_eval_cfkg_topk_workspace_bytes(d, nq, nc, int(topn), int(nsplit)), nq, topn,
-                       dev, with_scores)
+    return _topn_sweep(entry, args, getattr(L.load(), entry + '_workspace_bytes')(d, nq, nc, int(topn), int(nsplit)), nq, topn, dev,
+                       with_scores)
+
+
+TOPN_MAX, TOPN_WIDE_MAX = 16, 64       # csrc/ktup_topn.h: one key per lane of a 16-lane row; up to four such segments
+# Is the wide-list sweep the route of a model's evaluate_topk at 17 <= topn <= 64 when nobody says otherwise (library option
+# eval_wide_topn / KTUP_EVAL_WIDE_TOPN = -1; 0: never, the batch walk stays; 1: always)?  profiles/wide_topn_times.txt: the sweep
+# beats the walk by more than the larger spread in every world, cut-off and run (CFKG 1.5 - 2.3 x, inner products 3.1 - 3.6 x).  CFKG
+# takes it.  The inner-product models (BPRMF, FM, CKE, coFM) stay opt-in although theirs is the larger gain: that their evaluate_topk
+# declines topn 17 is what tests/test_hip_dot_pass.py::test_driver_pass_equals_the_batch_walk asserts, so flipping this entry is a
+# change of pinned behaviour and belongs with a rewrite of that test.
+WIDE_TOPN_DEFAULT = {'dot': False, 'cfkg_l1': True, 'cfkg_l2': True}
+
+
+def topk_sweep_for(topn, narrow, wide, model):
+    """The one-sweep wrapper that serves `topn` for `model` (a key of WIDE_TOPN_DEFAULT): `narrow` up to 16, `wide` for 17-64 where
+    it is the default or asked for, None (the caller keeps the batch walk) otherwise."""
+    if topn <= TOPN_MAX:
+        return narrow
+    if topn <= TOPN_WIDE_MAX:
+        opt = L.get_option('eval_wide_topn')
+        if opt > 0 or (opt < 0 and WIDE_TOPN_DEFAULT[model]):
+            return wide
+    return None
 
 
 def eval_tup(U, I, pref, pref_norm, u, l1, gumbel_mode=GUMBEL_OFF, uniform=None, seed=0, offset=0, items=None):

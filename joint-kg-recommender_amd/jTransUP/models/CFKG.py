@@ -67,8 +67,9 @@ class CFKG(nn.Module, GradToggle):
         the entity rows `items` (int64 ids; None = every row) AND their filtered top-n, without the (users x candidates) matrix.
         Ids in the filter lists and in the result are positions in `items`.  -> int32 (len(u_ids), topn), -1 padded, or None where
         the kernel declines the shape (the caller keeps the batch walk)."""
-        return ops.eval_cfkg_topk(self.user_embeddings.weight, self.rel_embeddings.weight, self.rel_total - 1, self.item_embeddings.weight,
-                                  u_ids, topn, self.L1_flag, cand_ids=items, filt_off=filt_off, filt_ids=filt_ids)
+        sweep = ops.topk_sweep_for(topn, ops.eval_cfkg_topk, ops.eval_cfkg_topk_wide, 'cfkg_l1' if self.L1_flag else 'cfkg_l2')
+        return sweep and sweep(self.user_embeddings.weight, self.rel_embeddings.weight, self.rel_total - 1, self.item_embeddings.weight,
+                               u_ids, topn, self.L1_flag, cand_ids=items, filt_off=filt_off, filt_ids=filt_ids)
 
     def _cand(self, all_e_ids):
         return self.ent_embeddings(all_e_ids).detach().contiguous() if all_e_ids is not None else None

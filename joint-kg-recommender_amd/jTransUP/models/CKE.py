@@ -79,8 +79,11 @@ class CKE(nn.Module, GradToggle):
         """`evaluateRec` + the filtered top-n for a whole evaluation pass in one sweep (this build), no (users x items) matrix.  The
         item side (item + aligned entity rows) is built inside the call, so a captured pass recomputes it from the tables.  `items`
         is unused; None where the sweep declines."""
+        sweep = ops.topk_sweep_for(topn, ops.eval_dot_topk, ops.eval_dot_topk_wide, 'dot')
+        if sweep is None:
+            return None
         with torch.no_grad():
-            return ops.eval_dot_topk(self.user_embeddings.weight, self._item_side().contiguous(), u_ids, topn, filt_off, filt_ids)
+            return sweep(self.user_embeddings.weight, self._item_side().contiguous(), u_ids, topn, filt_off, filt_ids)
 
     def prepare_entities(self):
         """Entity side of evaluateHead / evaluateTail, once per evaluation pass (`ents=`)."""

@@ -35,5 +35,7 @@ class BPRMF(nn.Module, GradToggle):
     def evaluate_topk(self, u_ids, items, topn, filt_off=None, filt_ids=None):
         """K11 + K17 for a whole evaluation pass in one sweep (this build): filtered top-n item ids of every user of `u_ids`
         without the (users x items) matrix; the scores and the order are `evaluate`'s + topk_filtered's, bit for bit.  `items` is
-        unused (this model has no prepared item side); None where the sweep declines (topn > 16, embedding_size > 256)."""
-        return ops.eval_dot_topk(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, topn, filt_off, filt_ids)
+        unused (this model has no prepared item side); None where the sweep declines (embedding_size > 256; topn > 16 unless the
+        wide lists serve it, ops.topk_sweep_for)."""
+        sweep = ops.topk_sweep_for(topn, ops.eval_dot_topk, ops.eval_dot_topk_wide, 'dot')
+        return sweep and sweep(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, topn, filt_off, filt_ids)

@@ -64,12 +64,13 @@ class coFM(nn.Module, GradToggle):
         """`evaluateRec` + the filtered top-n for a whole evaluation pass in one sweep (this build), own item table only: with
         shared tables the candidates are the item ids' rows of the entity table (all_i_ids) and the batch walk stays -> None.  The
         bias terms are formed by torch exactly as `evaluateRec` forms them.  `items` is unused; None where the sweep declines."""
-        if self.is_share:
+        sweep = None if self.is_share else ops.topk_sweep_for(topn, ops.eval_dot_topk, ops.eval_dot_topk_wide, 'dot')
+        if sweep is None:
             return None
         with torch.no_grad():
             user_add = self.bias + self.user_bias(u_ids)
-            return ops.eval_dot_topk(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, topn, filt_off, filt_ids,
-                                     user_add=user_add, item_add=self.item_bias.weight)
+            return sweep(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, topn, filt_off, filt_ids,
+                         user_add=user_add, item_add=self.item_bias.weight)
 
     def _cand(self, all_e_ids):
         return self.ent_embeddings(all_e_ids).detach().contiguous() if (all_e_ids is not None and self.is_share) else None

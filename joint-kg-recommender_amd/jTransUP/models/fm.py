@@ -55,7 +55,10 @@ class FM(nn.Module, GradToggle):
         """`evaluate` + the filtered top-n for a whole evaluation pass in one sweep (this build), no (users x items) matrix: the
         user-side and item-side bias terms are formed by torch exactly as `evaluate` forms them and added to the dot product in its
         order, so scores and order are the per-batch route's bits.  `items` is unused; None where the sweep declines."""
+        sweep = ops.topk_sweep_for(topn, ops.eval_dot_topk, ops.eval_dot_topk_wide, 'dot')
+        if sweep is None:
+            return None
         with torch.no_grad():
             user_add = self.bias + self.user_bias(u_ids)
-            return ops.eval_dot_topk(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, topn, filt_off, filt_ids,
-                                     user_add=user_add, item_add=self.item_bias.weight)
+            return sweep(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, topn, filt_off, filt_ids,
+                         user_add=user_add, item_add=self.item_bias.weight)
