@@ -631,9 +631,9 @@ struct ApplyRowsT {
         row = key;
       }
       const int64_t id = ids[row];
-      if (id < 0) return;
+      if (id < 0 && !xkeys) return;                      // (a LISTED row without an owner row is still cleared: gw is left all-zero)
       float* grow = g + row * ldg;
-      if (!skip) {
+      if (!skip && id >= 0) {
         const int t = wire_table(w, row);
         cx.load(gr, grow);
         one(cx, w.tab[t] + id * w.ldt[t], adagrad ? w.st[t] + id * w.lds[t] : nullptr, gr, coef);
