@@ -58,8 +58,9 @@ const char* ktup_last_error(void);
  *                                        and two runs of a step give the same bits (sums of float atomics issued by several
  *                                        workgroups depend on the order they land in).  For parity runs: ~50x slower.
  *   "eval_wide_topn" [KTUP_EVAL_WIDE_TOPN, -1]  read by the callers, not by the library: whether a model's evaluation pass at
- *                                        17 <= topn <= 64 takes ktup_eval_dot_topk_wide / ktup_eval_cfkg_topk_wide -- 0: never (the
- *                                        per-batch calls stay), 1: always, -1: where the caller's measured default says so          */
+ *                                        17 <= topn <= 64 takes its wide entry point (ktup_eval_dot_topk_wide, ktup_eval_cfkg_topk_wide,
+ *                                        ktup_eval_pref_topk_wide, ktup_eval_pref_topk_hard_wide) -- 0: never (the per-batch calls
+ *                                        stay), 1: always, -1: where the caller's measured default says so                          */
 int ktup_set_option(const char* name, int value);
 int ktup_get_option(const char* name, int* value);
 
@@ -312,6 +313,25 @@ int ktup_eval_pref_topk_hard(const float* U, int64_t ldu, const float* I, int64_
                              int64_t n_items, int l1, int gumbel_mode, const float* uniform, uint64_t seed, uint64_t offset,
                              const int64_t* filt_off, const int32_t* filt_ids, int topn, int32_t* top_ids, float* top_scores,
                              float* ws, void* stream);
+
+/* Both passes for cut-offs up to 64: the argument lists, rules, scores and list order of ktup_eval_pref_topk and
+ * ktup_eval_pref_topk_hard for 1 <= topn <= 64 (65: KTUP_ERR_UNSUPPORTED, workspace size 0).  The preference-space pass keeps a
+ * user's list as two (topn <= 32) or four 16-key segments (csrc/ktup_topn.h) at 8 or 24 KB more LDS per workgroup and two
+ * workgroups per CU; a (user, item) score is the same bits on either entry point.  The hard / soft sweeps keep the list across the
+ * 64 lanes of a wave as they do up to 16.  At most 512 / topn catalogue splits (and 8); values at or below 16 are accepted so that
+ * the two forms can be compared.  KTUP_ERR_UNSUPPORTED where the wider lists no longer fit the LDS beside the stage (the hybrid
+ * soft stage at d > 168 with the longer cut-offs).  `ws`: the matching *_wide_workspace_bytes bytes, 16-byte aligned.            */
+size_t ktup_eval_pref_topk_wide_workspace_bytes(int d, int n_pref, int64_t nq, int64_t n_items, int topn);
+int ktup_eval_pref_topk_wide(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
+                             const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids, int64_t nq,
+                             int64_t n_items, int l1, const int64_t* filt_off, const int32_t* filt_ids, int topn, int32_t* top_ids,
+                             float* top_scores, float* ws, void* stream);
+size_t ktup_eval_pref_topk_hard_wide_workspace_bytes(int d, int n_pref, int64_t nq, int64_t n_items, int topn);
+int ktup_eval_pref_topk_hard_wide(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
+                                  const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids, int64_t nq,
+                                  int64_t n_items, int l1, int gumbel_mode, const float* uniform, uint64_t seed, uint64_t offset,
+                                  const int64_t* filt_off, const int32_t* filt_ids, int topn, int32_t* top_ids, float* top_scores,
+                                  float* ws, void* stream);
 
 /* ------------------------------------------- K17/K18  ranking walk  utils/misc.py:125-146,213-248
  * Order: ascending score (descending != 0 negates first, misc.py:93,180), ties -> lower id (declared rule).
@@ -912,8 +932,8 @@ int ktup_eval_dot_topk(const float* U, int64_t ldu, const float* I, int64_t ldi,
  * workspace size 0).  A user's list is kept as two (topn <= 32) or four 16-key segments instead of one key per lane of a 16-lane
  * row, merged by a longer network and at more LDS per workgroup; values at or below 16 are accepted so that the two list forms can be
  * compared.  The split rule is the same 512 / topn, at most 32: 25 splits at topn 20, 8 at 64.  `ws`:
- * ktup_eval_dot_topk_wide_workspace_bytes bytes.  The sweeps of TUP / KTUP (ktup_eval_pref_topk, ktup_eval_pref_topk_hard) keep
- * lists of their own and decline above 16.                                                                                      */
+ * ktup_eval_dot_topk_wide_workspace_bytes bytes.  The sweeps of TUP / KTUP have wide entry points of their own
+ * (ktup_eval_pref_topk_wide, ktup_eval_pref_topk_hard_wide).                                                                     */
 size_t ktup_eval_dot_topk_wide_workspace_bytes(int d, int64_t nq, int64_t n_items, int topn, int nsplit);
 int ktup_eval_dot_topk_wide(const float* U, int64_t ldu, const float* I, int64_t ldi, int d, const int64_t* u_ids, int64_t nq,
                             int64_t n_items, const float* user_add, const float* item_add, const int64_t* filt_off,

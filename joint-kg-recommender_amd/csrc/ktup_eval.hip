@@ -1518,13 +1518,19 @@ extern "C" size_t ktup_eval_pref_topk_workspace_bytes(int d, int n_pref, int64_t
   if (nq <= 0 || topn <= 0 || n_items < 0) return 0;
   return ktup::eval_pass_pspace_bytes(d, n_pref, nq, n_items, topn);
 }
+// ... for lists of up to TOPN_WIDE_MAX keys (the partial lists sized by topn)
+extern "C" size_t ktup_eval_pref_topk_wide_workspace_bytes(int d, int n_pref, int64_t nq, int64_t n_items, int topn) {
+  if (nq <= 0 || topn <= 0 || topn > ktup::TOPN_WIDE_MAX || n_items < 0) return 0;
+  return ktup::eval_pass_pspace_bytes(d, n_pref, nq, n_items, topn, true);
+}
 
-extern "C" int ktup_eval_pref_topk(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
-                                   const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids, int64_t nq,
-                                   int64_t n_items, int l1, const int64_t* filt_off, const int32_t* filt_ids, int topn,
-                                   int32_t* top_ids, float* top_scores, float* ws, void* stream) {
-  const char* name = "ktup_eval_pref_topk";
+// the narrow and the wide entry point: the same arguments and rules, `wide` picks the list form (ktup_eval_pass.hip)
+static int pref_topk_entry(const char* name, bool wide, const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
+                           const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids, int64_t nq,
+                           int64_t n_items, int l1, const int64_t* filt_off, const int32_t* filt_ids, int topn,
+                           int32_t* top_ids, float* top_scores, float* ws, void* stream) {
   KTUP_REQUIRE(nq >= 0 && n_items >= 0 && topn > 0, "%s: bad sizes", name);
+  if (wide && topn > ktup::TOPN_WIDE_MAX) return set_error(KTUP_ERR_UNSUPPORTED, "%s: topn %d > %d", name, topn, ktup::TOPN_WIDE_MAX);
   if (nq == 0) return KTUP_OK;
   const PrefGeom g = pref_geom(d, n_pref);
   if (!g.ok || l1 || n_items == 0) return set_error(KTUP_ERR_UNSUPPORTED, "%s: squared-L2 soft gate, d %% 4 == 0 only", name);
@@ -1532,9 +1538,25 @@ extern "C" int ktup_eval_pref_topk(const float* U, int64_t ldu, const float* I, 
   KTUP_REQUIRE((E == nullptr) == (item2ent == nullptr), "%s: E and item2ent must be given together", name);
   KTUP_REQUIRE(aligned16(pref_ws) && aligned16(ws), "%s: workspaces must be 16-byte aligned", name);
   const int rc = ktup::eval_pass_pspace(U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, g.ppad, g.dp, n_pref, d, filt_off,
-                                        filt_ids, topn, ws, top_ids, top_scores, (hipStream_t)stream, name);
+                                        filt_ids, topn, ws, top_ids, top_scores, (hipStream_t)stream, name, wide);
   if (rc == 1) return set_error(KTUP_ERR_UNSUPPORTED, "%s: no fused pass kernel for d=%d, n_pref=%d, topn=%d", name, d, n_pref, topn);
   return rc;
+}
+
+extern "C" int ktup_eval_pref_topk(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
+                                   const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids, int64_t nq,
+                                   int64_t n_items, int l1, const int64_t* filt_off, const int32_t* filt_ids, int topn,
+                                   int32_t* top_ids, float* top_scores, float* ws, void* stream) {
+  return pref_topk_entry("ktup_eval_pref_topk", false, U, ldu, I, ldi, E, lde, item2ent, pref_ws, n_pref, d, u_ids, nq, n_items, l1, filt_off,
+                         filt_ids, topn, top_ids, top_scores, ws, stream);
+}
+// The same pass on the wide lists: 1 <= topn <= 64 (KTUP_ERR_UNSUPPORTED above), the scores the narrow pass's bits.
+extern "C" int ktup_eval_pref_topk_wide(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
+                                        const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids, int64_t nq,
+                                        int64_t n_items, int l1, const int64_t* filt_off, const int32_t* filt_ids, int topn,
+                                        int32_t* top_ids, float* top_scores, float* ws, void* stream) {
+  return pref_topk_entry("ktup_eval_pref_topk_wide", true, U, ldu, I, ldi, E, lde, item2ent, pref_ws, n_pref, d, u_ids, nq, n_items, l1,
+                         filt_off, filt_ids, topn, top_ids, top_scores, ws, stream);
 }
 
 extern "C" int ktup_eval_pref_scores(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
@@ -1570,15 +1592,29 @@ extern "C" size_t ktup_eval_pref_topk_hard_workspace_bytes(int d, int n_pref, in
   return (item_side_floats(n_items, d, n_pref) + user_side_floats(nq, d, n_pref)) * sizeof(float) + (size_t)nq * 8 * topn * sizeof(uint64_t) + 64;
 }
 
-extern "C" int ktup_eval_pref_topk_hard(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
-                                        const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids, int64_t nq,
-                                        int64_t n_items, int l1, int gumbel_mode, const float* uniform, uint64_t seed, uint64_t offset,
-                                        const int64_t* filt_off, const int32_t* filt_ids, int topn, int32_t* top_ids, float* top_scores,
-                                        float* ws, void* stream) {
-  const char* name = "ktup_eval_pref_topk_hard";
+// ... for lists of up to TOPN_WIDE_MAX keys (the same rule: both size the partial lists by topn)
+extern "C" size_t ktup_eval_pref_topk_hard_wide_workspace_bytes(int d, int n_pref, int64_t nq, int64_t n_items, int topn) {
+  if (topn > ktup::TOPN_WIDE_MAX) return 0;
+  return ktup_eval_pref_topk_hard_workspace_bytes(d, n_pref, nq, n_items, topn);
+}
+
+// The narrow (topn_cap = 16) and the wide (64) entry point.  The sweeps keep a user's list across the lanes of a wave (lane < topn:
+// sweep_rank), which holds 64 keys as it holds 16; what differs is here: the LDS the lists take beside the stage, at most 512 / topn
+// catalogue splits (and 8) and the merge over up to 512 keys per user for the wide form.
+static int pref_topk_hard_entry(const char* name, int topn_cap, const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E,
+                                int64_t lde, const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids,
+                                int64_t nq, int64_t n_items, int l1, int gumbel_mode, const float* uniform, uint64_t seed, uint64_t offset,
+                                const int64_t* filt_off, const int32_t* filt_ids, int topn, int32_t* top_ids, float* top_scores,
+                                float* ws, void* stream) {
+  const bool wide = topn_cap > ktup::TOPN_MAX;
   KTUP_REQUIRE(nq >= 0 && n_items >= 0, "%s: bad sizes", name);
+  if (wide) {
+    KTUP_REQUIRE(topn >= 1, "%s: bad sizes", name);
+    if (topn > topn_cap) return set_error(KTUP_ERR_UNSUPPORTED, "%s: topn %d > %d", name, topn, topn_cap);
+  }
   if (nq == 0) return KTUP_OK;
-  KTUP_REQUIRE(n_items > 0 && n_items < (1ll << 31) && topn >= 1 && topn <= 16 && n_pref <= 32, "%s: needs items, 32-bit item ids, topn <= 16 and at most 32 preferences", name);
+  KTUP_REQUIRE(n_items > 0 && n_items < (1ll << 31) && topn >= 1 && topn <= topn_cap && n_pref <= 32, "%s: needs items, 32-bit item ids, topn <= %d and at most 32 preferences", name, topn_cap);
+  const int max_splits = wide && 512 / topn < 8 ? 512 / topn : 8;
   KTUP_REQUIRE(gumbel_mode >= KTUP_GUMBEL_OFF && gumbel_mode <= KTUP_GUMBEL_PHILOX_DEV, "%s: bad gumbel_mode", name);
   KTUP_REQUIRE(U && I && pref_ws && u_ids && top_ids && ws && aligned16(ws), "%s: bad argument", name);
   KTUP_REQUIRE(gumbel_mode == KTUP_GUMBEL_OFF || gumbel_mode == KTUP_GUMBEL_PHILOX || uniform, "%s: KTUP_GUMBEL_INPUT / KTUP_GUMBEL_PHILOX_DEV need the `uniform` pointer", name);
@@ -1606,7 +1642,7 @@ extern "C" int ktup_eval_pref_topk_hard(const float* U, int64_t ldu, const float
     ss.filt_off = filt_off; ss.filt_ids = filt_ids; ss.topn = topn; ss.part = part;
     const int64_t ub = (nq + SS_NW * SS_UW - 1) / (SS_NW * SS_UW);
     int ns = (int)(256 / ub);                       // one workgroup per CU is resident (the stage is 77 KB at d = 100): one round
-    if (ns > 8) ns = 8;
+    if (ns > max_splits) ns = max_splits;
     if (ns < 1) ns = 1;
     const int64_t stg = (n_items + CT - 1) / CT;
     if (ns > stg) ns = (int)stg;
@@ -1629,7 +1665,7 @@ extern "C" int ktup_eval_pref_topk_hard(const float* U, int64_t ldu, const float
     if (whole) { if (l1) go(sweep_soft_kernel<true>); else go(sweep_soft_kernel<false>); }
     else { if (l1) go(sweep_soft_kernel<true, true>); else go(sweep_soft_kernel<false, true>); }
     if (int e = check_launch(name)) return e;
-    return ktup::launch_topk_merge(part, nq, ns, topn, top_ids, top_scores, st, name);
+    return ktup::launch_topk_merge(part, nq, ns, topn, wide, top_ids, top_scores, st, name);
   }
   SweepHardArgs sa{};
   HardArgs& h = sa.h;
@@ -1639,7 +1675,7 @@ extern "C" int ktup_eval_pref_topk_hard(const float* U, int64_t ldu, const float
   sa.filt_off = filt_off; sa.filt_ids = filt_ids; sa.topn = topn; sa.part = part;
   const int64_t ublocks = (nq + SW_NW * SW_UW - 1) / (SW_NW * SW_UW);
   int nsplit = (int)(768 / ublocks);                     // three workgroups per CU are resident (LDS): one round
-  if (nsplit > 8) nsplit = 8;
+  if (nsplit > max_splits) nsplit = max_splits;
   if (nsplit < 1) nsplit = 1;
   const int64_t stages = (n_items + CT - 1) / CT;
   if (nsplit > stages) nsplit = (int)stages;
@@ -1658,5 +1694,24 @@ extern "C" int ktup_eval_pref_topk_hard(const float* U, int64_t ldu, const float
   };
   if (l1) launch(sweep_hard_kernel<1>); else launch(sweep_hard_kernel<0>);
   if (int e = check_launch(name)) return e;
-  return ktup::launch_topk_merge(part, nq, nsplit, topn, top_ids, top_scores, st, name);
+  return ktup::launch_topk_merge(part, nq, nsplit, topn, wide, top_ids, top_scores, st, name);
+}
+
+extern "C" int ktup_eval_pref_topk_hard(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
+                                        const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids, int64_t nq,
+                                        int64_t n_items, int l1, int gumbel_mode, const float* uniform, uint64_t seed, uint64_t offset,
+                                        const int64_t* filt_off, const int32_t* filt_ids, int topn, int32_t* top_ids, float* top_scores,
+                                        float* ws, void* stream) {
+  return pref_topk_hard_entry("ktup_eval_pref_topk_hard", ktup::TOPN_MAX, U, ldu, I, ldi, E, lde, item2ent, pref_ws, n_pref, d, u_ids, nq,
+                              n_items, l1, gumbel_mode, uniform, seed, offset, filt_off, filt_ids, topn, top_ids, top_scores, ws, stream);
+}
+// The same sweeps with lists of up to 64 keys: 1 <= topn <= 64 (KTUP_ERR_UNSUPPORTED above, and where the lists do not fit the LDS
+// beside the stage), the scores and the order those of the narrow entry point.
+extern "C" int ktup_eval_pref_topk_hard_wide(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
+                                             const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids,
+                                             int64_t nq, int64_t n_items, int l1, int gumbel_mode, const float* uniform, uint64_t seed,
+                                             uint64_t offset, const int64_t* filt_off, const int32_t* filt_ids, int topn, int32_t* top_ids,
+                                             float* top_scores, float* ws, void* stream) {
+  return pref_topk_hard_entry("ktup_eval_pref_topk_hard_wide", ktup::TOPN_WIDE_MAX, U, ldu, I, ldi, E, lde, item2ent, pref_ws, n_pref, d, u_ids,
+                              nq, n_items, l1, gumbel_mode, uniform, seed, offset, filt_off, filt_ids, topn, top_ids, top_scores, ws, stream);
 }

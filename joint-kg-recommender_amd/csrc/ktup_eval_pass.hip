@@ -25,6 +25,11 @@
 //     prologue per workgroup.);
 //   * both operand tables and the per-row scalars are built per pass by one small launch (pspace_rows_kernel) after the three
 //     P x P Gram matrices (pspace_gram_kernel); the splits' partial lists are merged by a last, tiny launch (topk_merge_kernel).
+//   * cut-offs above 16 (ktup_eval_pref_topk_wide): the list is SEG = 2 (topn <= 32) or 4 (topn <= 64) of ktup_topn.h's 16-key
+//     segments, [16][SEG][16] keys per wave, merged by row_merge_pending_wide; everything that makes a score, the candidate test, the
+//     filter bit and the append are the same code, so a (user, item) score is the same bits on either entry point.  A segment adds
+//     2 KB per wave: two workgroups per CU instead of three, at most 512 / topn splits (and 8), the merge over up to 512 keys per user
+//     (topk_merge_kernel<8, .>).  SEG = 1 is the narrow entry point's kernel, the machine code it was before the parameter existed;
 // L1 distance and the ST-Gumbel gate do not decompose into bilinear terms: the hard gate has its own sweep (ktup_eval.hip
 // sweep_hard_kernel, either distance); the soft gate with L1 keeps the per-batch kernels of ktup_eval.hip.
 #include <hip/hip_runtime.h>
@@ -40,10 +45,19 @@ namespace ktup {
 namespace {
 
 constexpr int IBT = 16;        // items per LDS tile
-// LDS per wave of the sweep: user scalars [16][4] | filter bits [16][bm_words] | pending candidates [16][PCAP] u64 | lists [16][16] u64 |
-// n-th keys [16] u64
-constexpr size_t WAVE_TAIL = (size_t)16 * PCAP * 8 + (size_t)16 * 16 * 8 + (size_t)16 * 8;
-constexpr size_t wave_lds_bytes(int bm_words) { return (((size_t)16 * 4 * 4 + (size_t)16 * bm_words * 4 + 7) & ~(size_t)7) + WAVE_TAIL; }
+// LDS per wave of the sweep: user scalars [16][4] | filter bits [16][bm_words] | pending candidates [16][PCAP] u64 | lists [16][SEG][16]
+// u64 | n-th keys [16] u64.  SEG: 16-key segments of a user's list (ktup_topn.h: 1 = the narrow list, 2 or 4 = the wide ones).  The
+// kernel finds the last three from the END of its wave's share: WAVE_TAIL<SEG> is the one place that says how long that end is, for the
+// kernel and for the launch's LDS size alike.
+template <int SEG>
+constexpr size_t WAVE_TAIL = (size_t)16 * PCAP * 8 + (size_t)16 * 16 * SEG * 8 + (size_t)16 * 8;
+template <int SEG>
+constexpr size_t wave_lds_bytes(int bm_words) { return (((size_t)16 * 4 * 4 + (size_t)16 * bm_words * 4 + 7) & ~(size_t)7) + WAVE_TAIL<SEG>; }
+// Workgroups per CU the sweep is bounded and split for.  Narrow: what the registers allow (QGeom::MINW; ~50 KB of LDS at d = 100,
+// P = 20 and ml1m-size splits: three fit).  Wide: a segment adds 2 KB per wave, 8 KB per workgroup -- ~58 KB with two, ~74 KB with
+// four: two workgroups per CU, and 256 registers a lane.
+template <typename G, int SEG>
+constexpr int q_wgs() { return SEG == 1 ? G::MINW : 2; }
 
 // The filter lists of a pass as bits, built ONCE per pass instead of once per catalogue split inside the sweep (where the walk was 15 of
 // the sweep's 180 us: every split's workgroup of a user block repeated it, latency-bound, before its first tile): one wave per 16
@@ -151,8 +165,9 @@ struct QArgs {
   int dbg;                       // MEASUREMENT ONLY (option dbg_eval): 1 no ranking epilogue, 2 no item loads, 4 no workgroup barrier per tile, 8 no tiles at all
 };
 
-template <typename G>
-__global__ __launch_bounds__(256, G::MINW) void eval_pass_q_kernel(QArgs a) {
+template <typename G, int SEG = 1>
+__global__ __launch_bounds__(256, (q_wgs<G, SEG>())) void eval_pass_q_kernel(QArgs a) {
+  static_assert(SEG == 1 || SEG == 2 || SEG == 4, "a list is one, two or four 16-key segments");
   constexpr int RB4 = G::RB4, ROW4 = G::ROW4, KA = G::KA, KS = G::KS, DPW = G::DPW;
   constexpr int FA = G::FA, TA = G::TA, FS = G::FS, TS = G::TS, FN = G::FN, TN = G::TN;
   static_assert(G::SUB == 1, "one 16-item tile per buffer");
@@ -160,12 +175,12 @@ __global__ __launch_bounds__(256, G::MINW) void eval_pass_q_kernel(QArgs a) {
   v4* Xb = reinterpret_cast<v4*>(smem);                                   // [2][TILE_F4] item tiles
   const int tid = threadIdx.x, lane = tid & 63, kq = lane >> 4, j = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  char* wbase = reinterpret_cast<char*>(Xb + 2 * G::TILE_F4) + (size_t)w * wave_lds_bytes(a.bm_words);
+  char* wbase = reinterpret_cast<char*>(Xb + 2 * G::TILE_F4) + (size_t)w * wave_lds_bytes<SEG>(a.bm_words);
   float* usc = reinterpret_cast<float*>(wbase);                           // [16][4] user scalars
   uint32_t* bm = reinterpret_cast<uint32_t*>(usc + 64);                   // [16][bm_words] filter bits of this split
-  uint64_t* pbuf = reinterpret_cast<uint64_t*>(wbase + wave_lds_bytes(a.bm_words) - WAVE_TAIL);   // [16][PCAP] pending candidates
-  uint64_t* tk = pbuf + 16 * PCAP;                                        // [16][16] the users' sorted lists (touched by merges only)
-  uint64_t* thrk = tk + 16 * 16;                                          // [16] their n-th keys (read where floats cannot decide)
+  uint64_t* pbuf = reinterpret_cast<uint64_t*>(wbase + wave_lds_bytes<SEG>(a.bm_words) - WAVE_TAIL<SEG>);   // [16][PCAP] pending candidates
+  uint64_t* tk = pbuf + 16 * PCAP;                                        // [16][SEG][16] the users' sorted lists (touched by merges only)
+  uint64_t* thrk = tk + 16 * 16 * SEG;                                         // [16] their n-th keys (read where floats cannot decide)
   // Which (user block, split) this workgroup takes: workgroups go to the 8 XCDs round-robin in launch order and every XCD has an L2 of
   // its own, so with (blockIdx.x, blockIdx.y) taken as they come the 8 splits of a user block sit on 8 different XCDs and EVERY L2
   // fetches EVERY user row (8 x 6.6 MB over the fabric at ml1m size, ~10 us of prologue).  XCD x (launch-order ids x, x + 8, ...) takes
@@ -198,7 +213,7 @@ __global__ __launch_bounds__(256, G::MINW) void eval_pass_q_kernel(QArgs a) {
   for (int idx = tid; idx < 2 * G::TILE_F4; idx += 256) Xb[idx] = (v4){0.f, 0.f, 0.f, 0.f};   // row pads stay finite (x 0 operands)
   if (!use_bmg)
     for (int idx = lane; idx < 16 * a.bm_words; idx += 64) bm[idx] = 0u;
-  for (int idx = lane; idx < 16 * 16; idx += 64) tk[idx] = PKEY_MAX;
+  for (int idx = lane; idx < 16 * 16 * SEG; idx += 64) tk[idx] = PKEY_MAX;   // every segment of every list
   if (lane < 16) thrk[lane] = u0 + lane < a.nq ? PKEY_MAX : 0;            // rows past the end: nothing is ever below
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -322,14 +337,30 @@ __global__ __launch_bounds__(256, G::MINW) void eval_pass_q_kernel(QArgs a) {
       if (!__builtin_amdgcn_ballot_w64(all ? n > 0 : n >= 16)) continue;
       const int ur = 4 * kq + reg;
       const uint64_t* row = pbuf + ur * PCAP;
-      const uint64_t merged = row_merge_pending(tk[ur * 16 + j], row, n, topn, j);   // all four rows of the slot at once
-      tk[ur * 16 + j] = merged;
+      uint64_t merged;                                                            // the segment that holds the n-th key
+      if constexpr (SEG == 1) {
+        merged = row_merge_pending(tk[ur * 16 + j], row, n, topn, j);             // all four rows of the slot at once
+        tk[ur * 16 + j] = merged;
+      } else {
+        uint64_t* lst = tk + ur * 16 * SEG + j;                                   // element p = 16 s + j: key s of lane j
+        uint64_t seg[SEG];
+#pragma unroll
+        for (int s = 0; s < SEG; ++s) seg[s] = lst[16 * s];
+        row_merge_pending_wide<SEG>(seg, row, n, topn, j);
+        merged = seg[0];
+#pragma unroll
+        for (int s = 0; s < SEG; ++s) {
+          lst[16 * s] = seg[s];
+          if (s == (topn - 1) >> 4) merged = seg[s];
+        }
+      }
       pend[reg] = 0;
+      const int nj = SEG == 1 ? topn - 1 : (topn - 1) & 15;                       // the lane of the n-th key in its segment
       if (u0 + ur < a.nq) {                                                       // (rows past the end keep thrf = -inf, thrk = 0)
-        const uint32_t hi = (uint32_t)__shfl((int)(merged >> 32), rowbase + topn - 1, 64);
+        const uint32_t hi = (uint32_t)__shfl((int)(merged >> 32), rowbase + nj, 64);
         const float own = topn_key_score(hi);                                     // (NaN: list short)
         thrf[reg] = own;                                                          // (the next tile's refresh brings the shared bound back)
-        if (j == topn - 1) {
+        if (j == nj) {
           thrk[ur] = merged;
           // the splits of a user tell each other: non-negative floats order like their bits (a negative n-th score -- rounding of a
           // squared distance -- is published as 0: a weaker bound, still one)
@@ -441,11 +472,24 @@ __global__ __launch_bounds__(256, G::MINW) void eval_pass_q_kernel(QArgs a) {
     if (!(a.dbg & 4)) __syncthreads();
   }
   flush(true);
-  if (j < topn) {
+  if constexpr (SEG == 1) {
+    if (j < topn) {
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int64_t ur = u0 + 4 * kq + reg;
-      if (ur < a.nq) a.part[(ur * a.nsplit + sp) * topn + j] = tk[(4 * kq + reg) * 16 + j];
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t ur = u0 + 4 * kq + reg;
+        if (ur < a.nq) a.part[(ur * a.nsplit + sp) * topn + j] = tk[(4 * kq + reg) * 16 + j];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int s = 0; s < SEG; ++s) {
+      const int p = 16 * s + j;                                            // this lane's key of segment s
+      if (p >= topn) continue;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t ur = u0 + 4 * kq + reg;
+        if (ur < a.nq) a.part[(ur * a.nsplit + sp) * topn + p] = tk[(4 * kq + reg) * 16 * SEG + p];
+      }
     }
   }
 }
@@ -830,8 +874,13 @@ inline size_t filt_bm_bytes(int64_t nq, int64_t n_items) {
   return b <= ((size_t)128 << 20) ? b : 0;
 }
 
+// Catalogue splits a pass may use and the keys of a user's partial lists in the scratch: the narrow entry keeps 8 splits x TOPN_MAX
+// whatever topn is; the wide one sizes them by topn, with at most 512 / topn splits (what topk_merge_kernel<8, .> holds) and 8.
+inline int q_max_splits(int topn, bool wide) { return wide && 512 / topn < 8 ? 512 / topn : 8; }
+inline size_t q_part_keys(int topn, bool wide) { return wide ? (size_t)q_max_splits(topn, true) * topn : (size_t)8 * TOPN_MAX; }
+
 template <typename G>
-QScratch q_carve(void* scratch, int64_t nq, int64_t n_items) {
+QScratch q_carve(void* scratch, int64_t nq, int64_t n_items, size_t part_keys) {
   QScratch s;
   float* p = reinterpret_cast<float*>(scratch);
   s.grams = p; p += 3 * 32 * 32;
@@ -840,17 +889,19 @@ QScratch q_carve(void* scratch, int64_t nq, int64_t n_items) {
   s.SCU = p; p += (size_t)nq * 4;
   s.B = p; p += (size_t)n_items * G::GROW + 64;                  // (eval_pass_pspace_bytes counts the same)
   s.part = reinterpret_cast<uint64_t*>(p);
-  s.gthr = reinterpret_cast<int32_t*>(s.part + (size_t)nq * 8 * TOPN_MAX);  // (eval_pass_pspace_bytes: nq x 8 x topn keys, topn <= TOPN_MAX)
+  s.gthr = reinterpret_cast<int32_t*>(s.part + (size_t)nq * part_keys);     // (eval_pass_pspace_bytes: nq x q_part_keys)
   s.bm = reinterpret_cast<uint32_t*>(s.gthr + ((nq + 63) / 64) * 64);
   return s;
 }
 
-template <typename G>
+// SEG = 1: the narrow entry point's pass.  SEG = 2, 4: the wide one's (topn <= 16 SEG).
+template <typename G, int SEG = 1>
 int launch_q(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, const float* I, int64_t ldi, const float* E, int64_t lde,
              const int32_t* item2ent, int64_t n_items, const float* pref_ws,
              int ppad, int dp, int n_pref, const int64_t* filt_off, const int32_t* filt_ids, int topn, void* scratch, int32_t* top_ids,
              float* top_scores, hipStream_t st, const char* name) {
-  const QScratch q = q_carve<G>(scratch, nq, n_items);
+  constexpr bool WIDE = SEG > 1;
+  const QScratch q = q_carve<G>(scratch, nq, n_items, q_part_keys(topn, WIDE));
   const float* Alog = pref_ws;
   const float* Ar = pref_ws + (size_t)ppad * dp;
   const float* Cn = pref_ws + (size_t)(ppad + n_pref) * dp;
@@ -859,16 +910,32 @@ int launch_q(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, cons
   using R = RGeom<G::NCH, G::NP>;
   // the catalogue splits of the sweep (decided here: the filter bitmap is laid out by split)
   const int64_t ublocks = (nq + 63) / 64;
-  int nsplit = (int)(256 * G::MINW / ublocks);                            // MINW workgroups per CU are resident: ONE round
-  if (nsplit > 8) nsplit = 8;
-  if (opt_eval_nsplit() > 0 && opt_eval_nsplit() <= 8) nsplit = opt_eval_nsplit();   // measurement knob
+  const int max_splits = q_max_splits(topn, WIDE);
   const int64_t tiles = (n_items + IBT - 1) / IBT;
-  if (nsplit > tiles) nsplit = (int)tiles;
-  if (nsplit < 1) nsplit = 1;
-  const int64_t split_items = ((tiles + nsplit - 1) / nsplit) * IBT;
-  nsplit = (int)((n_items + split_items - 1) / split_items);
-  const int bm_words = (int)((split_items + 31) / 32);
-  const size_t lds = (size_t)2 * G::TILE_F4 * 16 + 4 * wave_lds_bytes(bm_words);
+  int nsplit, bm_words;
+  int64_t split_items;
+  size_t lds;
+  auto plan = [&](int resident) {                                         // `resident` workgroups per CU: ONE round
+    nsplit = (int)(256 * resident / ublocks);
+    if (nsplit > max_splits) nsplit = max_splits;
+    if (opt_eval_nsplit() > 0 && opt_eval_nsplit() <= max_splits) nsplit = opt_eval_nsplit();   // measurement knob
+    if (nsplit > tiles) nsplit = (int)tiles;
+    if (nsplit < 1) nsplit = 1;
+    split_items = ((tiles + nsplit - 1) / nsplit) * IBT;
+    nsplit = (int)((n_items + split_items - 1) / split_items);
+    bm_words = (int)((split_items + 31) / 32);
+    lds = (size_t)2 * G::TILE_F4 * 16 + 4 * wave_lds_bytes<SEG>(bm_words);
+  };
+  plan(q_wgs<G, SEG>());                                                  // (narrow: MINW, what the registers allow)
+  if (WIDE && 2 * lds > 160 * 1024) {
+    // the wide lists and this catalogue's filter bits leave room for one workgroup per CU: split for one, if the longer splits'
+    // filter bits still fit
+    const int ns = nsplit, bw = bm_words;
+    const int64_t si = split_items;
+    const size_t l = lds;
+    plan(1);
+    if (lds > 160 * 1024) { nsplit = ns; bm_words = bw; split_items = si; lds = l; }
+  }
   if (lds > 160 * 1024) return 1;
   const int gram_blocks = (3 * G::P4 * G::P4 + 3) / 4;
   const size_t bm_lds = (size_t)4 * 16 * nsplit * bm_words * sizeof(uint32_t);
@@ -899,24 +966,32 @@ int launch_q(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, cons
   a.filt_off = filt_off; a.filt_ids = filt_ids; a.topn = topn; a.part = q.part; a.dbg = opt_dbg_eval();
   a.split_items = split_items; a.nsplit = nsplit; a.bm_words = bm_words; a.bmg = use_bm ? q.bm : nullptr;
   a.gthr = nsplit > 1 && !(a.dbg & 64) ? q.gthr : nullptr;
-  (void)hipFuncSetAttribute((const void*)eval_pass_q_kernel<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((eval_pass_q_kernel<G>), dim3((unsigned)ublocks, (unsigned)nsplit), dim3(256), lds, st, a);
+  (void)hipFuncSetAttribute((const void*)eval_pass_q_kernel<G, SEG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((eval_pass_q_kernel<G, SEG>), dim3((unsigned)ublocks, (unsigned)nsplit), dim3(256), lds, st, a);
   if (int e = check_launch(name)) return e;
-  hipLaunchKernelGGL((topk_merge_kernel<2, false>), dim3((unsigned)((nq + 3) / 4)), dim3(MERGE_T), 0, st, q.part, nq, nsplit, topn, top_ids,
-                     top_scores);
-  return check_launch(name);
+  return launch_topk_merge(q.part, nq, nsplit, topn, WIDE, top_ids, top_scores, st, name);   // nsplit x topn <= 128 (narrow) / 512 keys per user
 }
 
-template <int NCH>
+template <int NCH, int SEG>
 int launch_q_p(int n_pref, const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, const float* I, int64_t ldi, const float* E,
                int64_t lde, const int32_t* item2ent, int64_t n_items,
                const float* pref_ws, int ppad, int dp, const int64_t* filt_off, const int32_t* filt_ids, int topn, void* scratch,
                int32_t* top_ids, float* top_scores, hipStream_t st, const char* name) {
   if (n_pref <= 4)
-    return launch_q<QGeom<NCH, 1>>(U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, n_pref, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
+    return launch_q<QGeom<NCH, 1>, SEG>(U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, n_pref, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
   if (n_pref <= 20)
-    return launch_q<QGeom<NCH, 5>>(U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, n_pref, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
-  return launch_q<QGeom<NCH, 8>>(U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, n_pref, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
+    return launch_q<QGeom<NCH, 5>, SEG>(U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, n_pref, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
+  return launch_q<QGeom<NCH, 8>, SEG>(U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, n_pref, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
+}
+
+template <int SEG>
+int launch_q_d(int d, int n_pref, const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, const float* I, int64_t ldi, const float* E,
+               int64_t lde, const int32_t* item2ent, int64_t n_items,
+               const float* pref_ws, int ppad, int dp, const int64_t* filt_off, const int32_t* filt_ids, int topn, void* scratch,
+               int32_t* top_ids, float* top_scores, hipStream_t st, const char* name) {
+  if (d == 64) return launch_q_p<16, SEG>(n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
+  if (d == 100) return launch_q_p<25, SEG>(n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
+  return launch_q_p<32, SEG>(n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
 }
 
 }  // namespace
@@ -925,33 +1000,42 @@ int launch_q_p(int n_pref, const float* U, int64_t ldu, const int64_t* u_ids, in
 
 namespace ktup {
 
-// the merge of the splits' partial lists, for the other sweeps (ktup_eval.hip: the hard gate's pass)
-int launch_topk_merge(const uint64_t* part, int64_t nq, int nsplit, int topn, int32_t* top_ids, float* top_scores, hipStream_t st, const char* name) {
-  hipLaunchKernelGGL((topk_merge_kernel<2, false>), dim3((unsigned)((nq + 3) / 4)), dim3(MERGE_T), 0, st, part, nq, nsplit, topn, top_ids,
-                     top_scores);
+// the merge of the splits' partial lists, for this pass and the other sweeps (ktup_eval.hip: the soft and the hard gate's passes).
+// Narrow: nsplit x topn <= 8 x 16 keys per user, two per lane; wide: <= 512, eight per lane.
+int launch_topk_merge(const uint64_t* part, int64_t nq, int nsplit, int topn, bool wide, int32_t* top_ids, float* top_scores, hipStream_t st,
+                      const char* name) {
+  if (wide)
+    hipLaunchKernelGGL((topk_merge_kernel<8, false>), dim3((unsigned)((nq + 3) / 4)), dim3(MERGE_T), 0, st, part, nq, nsplit, topn, top_ids,
+                       top_scores);
+  else
+    hipLaunchKernelGGL((topk_merge_kernel<2, false>), dim3((unsigned)((nq + 3) / 4)), dim3(MERGE_T), 0, st, part, nq, nsplit, topn, top_ids,
+                       top_scores);
   return check_launch(name);
 }
 
-// The preference-space pass (see QGeom): scratch for the Gram matrices, both operand tables, the scalars and the partial lists.
-size_t eval_pass_pspace_bytes(int d, int n_pref, int64_t nq, int64_t n_items, int topn) {
+// The preference-space pass (see QGeom): scratch for the Gram matrices, both operand tables, the scalars and the partial lists
+// (narrow: 8 x TOPN_MAX keys per user whatever topn is; wide: q_part_keys, by topn).
+size_t eval_pass_pspace_bytes(int d, int n_pref, int64_t nq, int64_t n_items, int topn, bool wide) {
   const size_t p4 = n_pref <= 4 ? 4 : n_pref <= 20 ? 20 : 32;
   const size_t ka = (d + 2 * p4 + 15) / 16, ks = (2 * p4 + 15) / 16, kn = (p4 + 15) / 16;
   const size_t arow = 16 * (ka + 2 * ks + kn), rowb = d + 3 * p4, grow = 4 * ((rowb / 4 + 1) | 1);      // QGeom::AROW, ROWB, GROW
-  (void)topn;
   return (3 * 32 * 32 + 4 * 2 * 8 * 64 + (size_t)nq * (arow + 4) + (size_t)n_items * grow + 64) * sizeof(float) +
-         (size_t)nq * 8 * TOPN_MAX * sizeof(uint64_t) + (size_t)((nq + 63) / 64) * 64 * sizeof(int32_t) + filt_bm_bytes(nq, n_items);
+         (size_t)nq * q_part_keys(topn, wide) * sizeof(uint64_t) + (size_t)((nq + 63) / 64) * 64 * sizeof(int32_t) + filt_bm_bytes(nq, n_items);
 }
 
 // Items: I[row] (+ E[item2ent[row]] for KTUP; E == NULL for TUP); pref_ws: the prepared tables (ktup_pref_prepare; ppad / dp its
-// geometry).  Returns KTUP_OK / an error, or 1 for shapes the pass does not cover.
+// geometry).  Returns KTUP_OK / an error, or 1 for shapes the pass does not cover.  wide: lists of two (topn <= 32) or four 16-key
+// segments for 1 <= topn <= TOPN_WIDE_MAX; the scores are the narrow pass's bits.
 int eval_pass_pspace(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, const float* I, int64_t ldi, const float* E, int64_t lde,
                      const int32_t* item2ent, int64_t n_items, const float* pref_ws,
                      int ppad, int dp, int n_pref, int d, const int64_t* filt_off, const int32_t* filt_ids, int topn, void* scratch,
-                     int32_t* top_ids, float* top_scores, hipStream_t st, const char* name) {
-  if ((d != 64 && d != 100 && d != 128) || n_pref < 1 || n_pref > 32 || topn < 1 || topn > TOPN_MAX || n_items >= (1ll << 31)) return 1;
-  if (d == 64) return launch_q_p<16>(n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
-  if (d == 100) return launch_q_p<25>(n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
-  return launch_q_p<32>(n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
+                     int32_t* top_ids, float* top_scores, hipStream_t st, const char* name, bool wide) {
+  if ((d != 64 && d != 100 && d != 128) || n_pref < 1 || n_pref > 32 || topn < 1 || topn > (wide ? TOPN_WIDE_MAX : TOPN_MAX) ||
+      n_items >= (1ll << 31))
+    return 1;
+  if (!wide) return launch_q_d<1>(d, n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
+  if (topn <= 32) return launch_q_d<2>(d, n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
+  return launch_q_d<4>(d, n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
 }
 
 }  // namespace ktup

@@ -83,7 +83,9 @@ int kg_query_prep(int model, const float* E, int64_t lde, const float* R, int64_
                   const int64_t* q, const int64_t* r, int64_t nq, int head, float* QW, hipStream_t st, const char* name);
 
 // ktup_eval_pass.hip: scores + filtered top-n of a whole evaluation pass in one launch (+ a merge launch).  1 = not covered.
-size_t eval_pass_pspace_bytes(int d, int n_pref, int64_t nq, int64_t n_items, int topn);
+// `wide`: the wide entry points' form (lists of up to TOPN_WIDE_MAX keys in 16-key segments, partial lists sized by topn, the merge
+// over up to 512 keys per user); false: the narrow entry points', as they were.
+size_t eval_pass_pspace_bytes(int d, int n_pref, int64_t nq, int64_t n_items, int topn, bool wide = false);
 int kg_valu_counts(int model, const float* QW, int d, const float* C, int64_t ldc, int64_t n_cand, int64_t nq, int l1, int descending,
                    const int64_t* gold_off, const int32_t* gold_ids, const int64_t* filt_off, const int32_t* filt_ids, float* gscore,
                    float* fscore, int32_t* counts, const int64_t* rel, const float* Nrm, int64_t ldn, int64_t n_rel, float* wtab, int64_t ldw,
@@ -101,11 +103,12 @@ int transr_pair_counts(const float* QW, int d, const float* PE, int64_t n_ent, i
 int kg_rank_finalize(const int64_t* gold_off, const int32_t* gold_ids, const float* gscore, const int64_t* filt_off, const int32_t* filt_ids,
                      float* fscore, int32_t* counts, int32_t* ranks, int64_t nq, int64_t n_cand, int64_t n_gold, int descending,
                      hipStream_t st, const char* name);
-int launch_topk_merge(const uint64_t* part, int64_t nq, int nsplit, int topn, int32_t* top_ids, float* top_scores, hipStream_t st, const char* name);
+int launch_topk_merge(const uint64_t* part, int64_t nq, int nsplit, int topn, bool wide, int32_t* top_ids, float* top_scores, hipStream_t st,
+                      const char* name);
 int eval_pass_pspace(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, const float* I, int64_t ldi, const float* E, int64_t lde,
                      const int32_t* item2ent, int64_t n_items, const float* pref_ws,
                      int ppad, int dp, int n_pref, int d, const int64_t* filt_off, const int32_t* filt_ids, int topn, void* scratch,
-                     int32_t* top_ids, float* top_scores, hipStream_t st, const char* name);
+                     int32_t* top_ids, float* top_scores, hipStream_t st, const char* name, bool wide = false);
 int pairs_kg_l2_mc(int model, const float* QW, int dq, const float* C, int64_t ldc, int d, int64_t nq, int64_t n_cand, float* out,
                    int64_t ldo, hipStream_t st, const char* name, const float* qcc = nullptr,
                    const float* cnorm = nullptr, const int32_t* qrel = nullptr);

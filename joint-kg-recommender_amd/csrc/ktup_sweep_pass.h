@@ -15,7 +15,7 @@
 // points launch; SEG = 2 and 4 (topn <= 32, <= 64) are the wide entry points' (ktup_eval_dot_topk_wide, ktup_eval_cfkg_topk_wide).
 // A wide list costs 2 or 6 KB more LDS per wave and a longer merge network; scorers, stages, filter bits, pending rows and the
 // append are the same code, so a score is the same bits at every width.  The sweeps of TUP / KTUP (ktup_eval_pass.hip,
-// ktup_eval.hip) have list code of their own and stay at 16.  Measured against the batch walk, which was all there was above 16
+// ktup_eval.hip) have pass bodies of their own; the first keeps its lists in the same segments.  Measured against the batch walk, which was all there was above 16
 // (profiles/wide_topn_times.txt, whole pass through the driver): inner products 6040 x 3240, d = 64: topn 20 0.85 -> 0.25 ms, topn 50
 // 1.52 -> 0.49 ms; 512 x 100,000: 1.65 -> 0.46 and 3.40 -> 1.05 ms; CFKG at d = 100: 1.31 -> 0.84 (L1) and 1.19 -> 0.65 ms (squared
 // L2) at topn 20.  The registers of a wide kernel are bounded for the workgroups per CU its LDS admits (sweep_wide_wgs); no wide

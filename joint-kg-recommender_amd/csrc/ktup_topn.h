@@ -5,7 +5,7 @@
 // lane of a 16-lane row) in LDS and touches it only when 16 candidates are pending for it; the catalogue splits' partial lists
 // are merged by topk_merge_kernel.  How a sweep keeps and renews its thresholds is its own business.
 // Two list widths: the NARROW list above (topn <= TOPN_MAX = 16; every sweep), and the WIDE list of SEG = 2 or 4 such 16-key
-// segments (topn <= 16 SEG <= TOPN_WIDE_MAX = 64; ktup_sweep_pass.h only): element p of a user's list is key (p >> 4) of lane
+// segments (topn <= 16 SEG <= TOPN_WIDE_MAX = 64; ktup_sweep_pass.h and ktup_eval_pass.hip): element p of a user's list is key (p >> 4) of lane
 // p & 15, so a lane holds SEG keys.  Pending buffer, append and merge kernel are the same for both.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -86,6 +86,11 @@ SIGNATURES = {
     'ktup_eval_pref_topk_hard_workspace_bytes': [c_i, c_i, c_l, c_l, c_i],
     'ktup_eval_pref_topk_hard': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_p, c_l, c_l, c_i, c_i, c_p, c_u, c_u, c_p, c_p, c_i, c_p,
                                  c_p, c_p, c_p],
+    'ktup_eval_pref_topk_wide_workspace_bytes': [c_i, c_i, c_l, c_l, c_i],
+    'ktup_eval_pref_topk_wide': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_p, c_l, c_l, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p],
+    'ktup_eval_pref_topk_hard_wide_workspace_bytes': [c_i, c_i, c_l, c_l, c_i],
+    'ktup_eval_pref_topk_hard_wide': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_p, c_l, c_l, c_i, c_i, c_p, c_u, c_u, c_p, c_p, c_i,
+                                      c_p, c_p, c_p, c_p],
     'ktup_eval_topk_filtered': [c_p, c_l, c_l, c_l, c_i, c_p, c_p, c_i, c_p, c_p, c_p],
     'ktup_eval_gold_rank_counts': [c_p, c_l, c_l, c_l, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     'ktup_eval_gold_rank_counts_strided': [c_p, c_l, c_l, c_l, c_l, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
@@ -201,6 +206,7 @@ _RESTYPE = {'ktup_last_error': ctypes.c_char_p, 'ktup_shard_reduce_list_len': ct
             'ktup_eval_kg_ranks_transd_workspace_bytes': ctypes.c_size_t, 'ktup_eval_dot_topk_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_cfkg_topk_workspace_bytes': ctypes.c_size_t, 'ktup_eval_dot_topk_wide_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_cfkg_topk_wide_workspace_bytes': ctypes.c_size_t,
+            'ktup_eval_pref_topk_wide_workspace_bytes': ctypes.c_size_t, 'ktup_eval_pref_topk_hard_wide_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_kg_ranks_transd_fused_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_kg_ranks_transr_fused_workspace_bytes': ctypes.c_size_t,
             'ktup_feed_align_lists_workspace_bytes': ctypes.c_size_t}

@@ -853,23 +853,45 @@ def eval_pref_topk(U, u, items, l1, topn, filt_off=None, filt_ids=None, with_sco
     """Scores + filtered top-n of a whole evaluation pass in one sweep (ktup_eval_pref_topk): every user of `u` against the
     item tables of `items`, no (users x items) matrix.  Squared L2 at d in {64, 100, 128}: the preference-space pass on the matrix cores;
     L1 and other widths: the pair kernel's arithmetic swept with the top-n in its epilogue (the per-batch scores' bits).  -> int32
-    (len(u), topn) ids (-1 padded) [, scores], or None when no sweep covers the shape (topn > 16, very wide rows): keep eval_tup /
-    eval_ktup + topk_filtered."""
+    (len(u), topn) ids (-1 padded) [, scores], or None when no sweep covers the shape (topn > 16: eval_pref_topk_wide; very wide
+    rows): keep eval_tup / eval_ktup + topk_filtered."""
+    return _eval_pref_topk('ktup_eval_pref_topk', TOPN_MAX, eval_pref_topk_hard, U, u, items, l1, topn, filt_off, filt_ids, with_scores)
+
+
+@torch.no_grad()
+def eval_pref_topk_wide(U, u, items, l1, topn, filt_off=None, filt_ids=None, with_scores=False):
+    """eval_pref_topk on the wide lists (ktup_eval_pref_topk_wide): the same arguments, scores and order for 1 <= topn <= 64.  L1,
+    other widths and eval_mc = 0 go to eval_pref_topk_hard_wide as the narrow wrapper's go to eval_pref_topk_hard.  None for
+    topn > 64, d > 256, P > 32 and where the library declines the shape."""
+    return _eval_pref_topk('ktup_eval_pref_topk_wide', TOPN_WIDE_MAX, eval_pref_topk_hard_wide, U, u, items, l1, topn, filt_off, filt_ids,
+                           with_scores)
+
+
+def pref_pass_covers(items, l1):
+    """Does the preference-space pass (soft gate) serve these item tables, or does the pair kernel's sweep?"""
+    return not l1 and items.d in (64, 100, 128) and bool(L.get_option('eval_mc'))
+
+
+def _eval_pref_topk(entry, topn_max, hard, U, u, items, l1, topn, filt_off, filt_ids, with_scores):
     U, u = _pad_users(U, u)
     dev = _dev(_table('user table', U))
     u = _ids('u_ids', u, dev)
     nq, d, P = u.numel(), items.d, items.P
-    if not (0 < topn <= 16) or nq == 0 or d > 256:
+    if not (0 < topn <= topn_max) or nq == 0 or d > 256:
         return None
-    if l1 or d not in (64, 100, 128) or not L.get_option('eval_mc'):
+    if not pref_pass_covers(items, l1):
         # no preference-space pass for this shape: the pair kernel's arithmetic with the top-n in its epilogue (or None: per-batch calls)
-        return eval_pref_topk_hard(U, u, items, l1, topn, GUMBEL_OFF, None, 0, 0, filt_off, filt_ids, with_scores)
+        return hard(U, u, items, l1, topn, GUMBEL_OFF, None, 0, 0, filt_off, filt_ids, with_scores)
+    wide = topn_max > TOPN_MAX
+    if wide and P > 32:
+        return None
     filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
     I, E = items.I, items.E
     args = (_p(U), U.stride(0), _p(I), I.stride(0), _p(E), 0 if E is None else E.stride(0), _p(items.item2ent), _p(items.pws), P, d, _p(u),
             nq, items.n_items, 0, _p(filt_off), _p(filt_ids), int(topn))
-    return _topn_sweep('ktup_eval_pref_topk', args, L.load().ktup_eval_pref_topk_workspace_bytes(d, P, nq, items.n_items, topn), nq, topn,
-                       dev, with_scores, may_decline=False)
+    # (the wide pass may decline: a catalogue whose filter bits no longer fit the LDS beside the longer lists)
+    return _topn_sweep(entry, args, getattr(L.load(), entry + '_workspace_bytes')(d, P, nq, items.n_items, topn), nq, topn,
+                       dev, with_scores, may_decline=wide)
 
 
 @torch.no_grad()
@@ -877,12 +899,26 @@ def eval_pref_topk_hard(U, u, items, l1, topn, gumbel_mode, uniform=None, seed=0
     """The hard (ST-Gumbel) gate's whole evaluation pass in one sweep (ktup_eval_pref_topk_hard): the scores of eval_tup / eval_ktup
     for the same noise source over ALL users of `u` at once (pair (b, j) draws at ((b n_items + j) P + p) + offset), L1 or squared
     L2, with the filtered top-n taken where the scores are made.  -> int32 (len(u), topn) ids (-1 padded) [, scores]; None when
-    topn > 16 or the library declines the shape (keep eval_* + topk_filtered)."""
+    topn > 16 (eval_pref_topk_hard_wide) or the library declines the shape (keep eval_* + topk_filtered)."""
+    return _eval_pref_topk_hard('ktup_eval_pref_topk_hard', TOPN_MAX, U, u, items, l1, topn, gumbel_mode, uniform, seed, offset, filt_off,
+                                filt_ids, with_scores)
+
+
+@torch.no_grad()
+def eval_pref_topk_hard_wide(U, u, items, l1, topn, gumbel_mode, uniform=None, seed=0, offset=0, filt_off=None, filt_ids=None,
+                             with_scores=False):
+    """eval_pref_topk_hard for 1 <= topn <= 64 (ktup_eval_pref_topk_hard_wide): the same arguments, score bits and order.  None for
+    topn > 64, d > 256, P > 32 and where the library declines (the lists no longer fit the LDS beside the stage)."""
+    return _eval_pref_topk_hard('ktup_eval_pref_topk_hard_wide', TOPN_WIDE_MAX, U, u, items, l1, topn, gumbel_mode, uniform, seed, offset,
+                                filt_off, filt_ids, with_scores)
+
+
+def _eval_pref_topk_hard(entry, topn_max, U, u, items, l1, topn, gumbel_mode, uniform, seed, offset, filt_off, filt_ids, with_scores):
     U, u = _pad_users(U, u)
     dev = _dev(_table('user table', U))
     u = _ids('u_ids', u, dev)
     nq, d, P, ni = u.numel(), items.d, items.P, items.n_items
-    if not (0 < topn <= 16) or nq == 0 or P > 32 or d > 256:
+    if not (0 < topn <= topn_max) or nq == 0 or P > 32 or d > 256:
         return None
     if gumbel_mode == GUMBEL_INPUT:
         uniform = _input_uniform(uniform, nq, ni, P, dev)
@@ -895,8 +931,7 @@ def eval_pref_topk_hard(U, u, items, l1, topn, gumbel_mode, uniform=None, seed=0
     args = (_p(U), U.stride(0), _p(I), I.stride(0), _p(E), 0 if E is None else E.stride(0), _p(items.item2ent), _p(items.pws), P, d, _p(u),
             nq, ni, int(l1), int(gumbel_mode), _p(uniform), int(seed), int(offset), _p(filt_off), _p(filt_ids), int(topn))
     # (declined: a shape the sweep does not cover -- a catalogue split whose filter bitmap passes the LDS; the caller keeps the per-batch calls)
-    return _topn_sweep('ktup_eval_pref_topk_hard', args, L.load().ktup_eval_pref_topk_hard_workspace_bytes(d, P, nq, ni, topn), nq, topn,
-                       dev, with_scores)
+    return _topn_sweep(entry, args, getattr(L.load(), entry + '_workspace_bytes')(d, P, nq, ni, topn), nq, topn, dev, with_scores)
 
 
 @torch.no_grad()
@@ -986,16 +1021,23 @@ TOPN_MAX, TOPN_WIDE_MAX = 16, 64       # csrc/ktup_topn.h: one key per lane of a
 # declines topn 17 is what tests/test_hip_dot_pass.py::test_driver_pass_equals_the_batch_walk asserts, so flipping this entry is a
 # change of pinned behaviour and belongs with a rewrite of that test.
 WIDE_TOPN_DEFAULT = {'dot': False, 'cfkg_l1': True, 'cfkg_l2': True}
+# The same question for TUP / KTUP, by the route a call takes: 'pref_q' the preference-space pass (soft gate, squared L2, d in {64, 100,
+# 128}), 'pref_soft' the pair kernel's sweep (soft gate with L1 or another width), 'pref_hard' the ST-Gumbel gate's sweep.  The rule
+# is the one above, on profiles/pref_wide_topn_times.txt (tools/pref_wide_topn_time.py: ml1m size, d = 100, P = 20, topn 20 and 50, two
+# runs): every gain exceeds the larger spread in both runs and at both cut-offs -- pref_q 4.3 - 4.7 x (TUP and KTUP), pref_soft 2.6 - 3.2 x
+# (KTUP with L1; 1.8 - 2.1 x at d = 256), pref_hard 1.4 - 1.9 x (L1 and squared L2) -- so all three take the wide pass.
+PREF_WIDE_TOPN_DEFAULT = {'pref_q': True, 'pref_soft': True, 'pref_hard': True}
 
 
 def topk_sweep_for(topn, narrow, wide, model):
-    """The one-sweep wrapper that serves `topn` for `model` (a key of WIDE_TOPN_DEFAULT): `narrow` up to 16, `wide` for 17-64 where
-    it is the default or asked for, None (the caller keeps the batch walk) otherwise."""
+    """The one-sweep wrapper that serves `topn` for `model` (a key of WIDE_TOPN_DEFAULT or of PREF_WIDE_TOPN_DEFAULT): `narrow` up to
+    16, `wide` for 17-64 where it is the default or asked for, None (the caller keeps the batch walk) otherwise."""
     if topn <= TOPN_MAX:
         return narrow
     if topn <= TOPN_WIDE_MAX:
         opt = L.get_option('eval_wide_topn')
-        if opt > 0 or (opt < 0 and WIDE_TOPN_DEFAULT[model]):
+        default = WIDE_TOPN_DEFAULT[model] if model in WIDE_TOPN_DEFAULT else PREF_WIDE_TOPN_DEFAULT[model]
+        if opt > 0 or (opt < 0 and default):
             return wide
     return None
 
