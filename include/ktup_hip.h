@@ -60,7 +60,11 @@ const char* ktup_last_error(void);
  *   "eval_wide_topn" [KTUP_EVAL_WIDE_TOPN, -1]  read by the callers, not by the library: whether a model's evaluation pass at
  *                                        17 <= topn <= 64 takes its wide entry point (ktup_eval_dot_topk_wide, ktup_eval_cfkg_topk_wide,
  *                                        ktup_eval_pref_topk_wide, ktup_eval_pref_topk_hard_wide) -- 0: never (the per-batch calls
- *                                        stay), 1: always, -1: where the caller's measured default says so                          */
+ *                                        stay), 1: always, -1: where the caller's measured default says so
+ *   "eval_q256"   [KTUP_EVAL_Q256, -1]   read by the callers, not by the library: whether a TUP / KTUP evaluation pass at d = 256
+ *                                        (soft gate, squared L2) takes the preference-space pass (ktup_eval_pref_topk / _wide) -- 1:
+ *                                        yes, 0: the pair kernel's sweep (ktup_eval_pref_topk_hard / _hard_wide with
+ *                                        KTUP_GUMBEL_OFF), -1: the caller's default.  No effect at any other width                */
 int ktup_set_option(const char* name, int value);
 int ktup_get_option(const char* name, int* value);
 
@@ -291,8 +295,11 @@ int ktup_eval_pref_scores_prepared(const float* U, int64_t ldu, const float* pre
  * batch by batch.  Straight from the tables: items are I[row] (+ E[item2ent[row]] for KTUP; E == item2ent == NULL for TUP),
  * pref_ws the prepared preference tables (ktup_pref_prepare).  Every user x item cross term except u.v is contracted in
  * preference space (csrc/ktup_eval_pass.hip): scores agree with ktup_eval_pref_scores to fp32 rounding, the order is the
- * (score, id) order of ktup_eval_topk_filtered.  Soft gate, squared L2 (l1 == 0), d in {64, 100, 128}, n_pref <= 32,
- * topn <= 16; otherwise KTUP_ERR_UNSUPPORTED and the caller keeps the per-batch pair of calls.  filt_off / filt_ids: CSR filter
+ * (score, id) order of ktup_eval_topk_filtered.  Soft gate, squared L2 (l1 == 0), d in {64, 100, 128, 256}, n_pref <= 32,
+ * topn <= 16; otherwise KTUP_ERR_UNSUPPORTED and the caller keeps the per-batch pair of calls.  d = 256: the user operands are up
+ * to 120 registers a lane (two workgroups per CU) and an item tile 18 - 23 KB, so a catalogue split whose filter bits no longer fit
+ * the 160 KB of LDS beside two tiles is KTUP_ERR_UNSUPPORTED too; the operand rows of n_pref > 4 are made one wave per row (the
+ * matrix-core row kernel's tables do not fit the LDS at this width).  filt_off / filt_ids: CSR filter
  * sets per user of u_ids (NULL = none); top_scores may be NULL.  `ws`: ktup_eval_pref_topk_workspace_bytes bytes, 16-byte aligned. */
 size_t ktup_eval_pref_topk_workspace_bytes(int d, int n_pref, int64_t nq, int64_t n_items, int topn);
 int ktup_eval_pref_topk(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
@@ -306,7 +313,8 @@ int ktup_eval_pref_topk(const float* U, int64_t ldu, const float* I, int64_t ldi
  * ((b * n_items + j) * n_pref + p) + offset -- with the filtered top-n taken where the scores are made (KTUP_GUMBEL_INPUT: uniform
  * is (nq x n_items x n_pref)); any d % 4 == 0, n_pref <= 32, topn <= 16.  gumbel_mode == KTUP_GUMBEL_OFF: the SOFT gate scored pair
  * by pair (the arithmetic of ktup_eval_pref_scores, its bits) with the same epilogue -- the one-sweep pass for L1 and for widths
- * ktup_eval_pref_topk does not cover (d <= 168); KTUP_ERR_UNSUPPORTED where the stage does not fit the LDS.                    */
+ * ktup_eval_pref_topk does not cover (d <= 168; d = 256 with a hybrid stage, the route of that width unless option "eval_q256"
+ * sends it to ktup_eval_pref_topk); KTUP_ERR_UNSUPPORTED where the stage does not fit the LDS.                                   */
 size_t ktup_eval_pref_topk_hard_workspace_bytes(int d, int n_pref, int64_t nq, int64_t n_items, int topn);
 int ktup_eval_pref_topk_hard(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
                              const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids, int64_t nq,

@@ -30,6 +30,9 @@
 //     filter bit and the append are the same code, so a (user, item) score is the same bits on either entry point.  A segment adds
 //     2 KB per wave: two workgroups per CU instead of three, at most 512 / topn splits (and 8), the merge over up to 512 keys per user
 //     (topk_merge_kernel<8, .>).  SEG = 1 is the narrow entry point's kernel, the machine code it was before the parameter existed;
+//   * d = 256 (QGeom<64, NP>): 71 / 99 / 120 operand registers a lane at P <= 4 / 20 / 32 (188 / 222 / 244 VGPRs in all, no scratch: two
+//     workgroups per CU, as at d = 128 with P > 4), tiles of 17.7 / 20.7 / 22.8 KB; the operand rows of P > 4 come from pspace_rows_kernel
+//     (RGeom<64, 5 | 8>::LDS is 176 / 182 KB: launch_q's ROWS_MC_FITS).  The callers take this width by option eval_q256;
 // L1 distance and the ST-Gumbel gate do not decompose into bilinear terms: the hard gate has its own sweep (ktup_eval.hip
 // sweep_hard_kernel, either distance); the soft gate with L1 keeps the per-batch kernels of ktup_eval.hip.
 #include <hip/hip_runtime.h>
@@ -905,9 +908,12 @@ int launch_q(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, cons
   const float* Alog = pref_ws;
   const float* Ar = pref_ws + (size_t)ppad * dp;
   const float* Cn = pref_ws + (size_t)(ppad + n_pref) * dp;
-  const bool rows_mc = opt_eval_mc() && !((ldu | ldi | lde | dp) & 3) && aligned16(U) && aligned16(I) && (!E || aligned16(E)) && aligned16(pref_ws) &&
-                       nq < (1ll << 31) && n_items < (1ll << 31);
   using R = RGeom<G::NCH, G::NP>;
+  // d = 256: the three staged tables + the Gram operands + four wave tiles of the matrix-core row kernel pass the LDS of a CU at P > 4
+  // (RGeom<64, 5>::LDS = 176 KB, <64, 8> 182 KB; <64, 1> 118 KB fits): those take the one-wave-per-row kernel, which stages nothing
+  constexpr bool ROWS_MC_FITS = R::LDS <= 160 * 1024;
+  const bool rows_mc = ROWS_MC_FITS && opt_eval_mc() && !((ldu | ldi | lde | dp) & 3) && aligned16(U) && aligned16(I) && (!E || aligned16(E)) &&
+                       aligned16(pref_ws) && nq < (1ll << 31) && n_items < (1ll << 31);
   // the catalogue splits of the sweep (decided here: the filter bitmap is laid out by split)
   const int64_t ublocks = (nq + 63) / 64;
   const int max_splits = q_max_splits(topn, WIDE);
@@ -951,11 +957,13 @@ int launch_q(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, cons
   RowsSide us{U, ldu, u_ids, nullptr, 0, nullptr, nq, q.A, G::AROW, q.SCU, grid_for((nq + 3) / 4, 2048), G::AROW, 4, q.gthr};
   RowsSide is{I, ldi, nullptr, E, lde, item2ent, n_items, q.B, G::ROWB, q.B + G::ROWB, grid_for((n_items + 3) / 4, 2048), G::GROW, G::GROW, nullptr};
   if (rows_mc) {    // 16 rows per wave on the matrix cores
-    us.blocks = (int)((nq + 63) / 64); is.blocks = (int)((n_items + 63) / 64);
-    const size_t rows_lds = use_bm && bm_lds > R::LDS ? bm_lds : R::LDS;
-    (void)hipFuncSetAttribute((const void*)pspace_rows_mc_kernel<G::NCH, G::NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds);
-    hipLaunchKernelGGL((pspace_rows_mc_kernel<G::NCH, G::NP>), dim3(us.blocks + is.blocks + (use_bm ? (unsigned)ublocks : 0u)), dim3(256), rows_lds, st,
-                       us, is, n_pref, Alog, Ar, Cn, dp, q.gs, G::KA, G::KS, fb);
+    if constexpr (ROWS_MC_FITS) {
+      us.blocks = (int)((nq + 63) / 64); is.blocks = (int)((n_items + 63) / 64);
+      const size_t rows_lds = use_bm && bm_lds > R::LDS ? bm_lds : R::LDS;
+      (void)hipFuncSetAttribute((const void*)pspace_rows_mc_kernel<G::NCH, G::NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds);
+      hipLaunchKernelGGL((pspace_rows_mc_kernel<G::NCH, G::NP>), dim3(us.blocks + is.blocks + (use_bm ? (unsigned)ublocks : 0u)), dim3(256), rows_lds, st,
+                         us, is, n_pref, Alog, Ar, Cn, dp, q.gs, G::KA, G::KS, fb);
+    }
   } else {
     hipLaunchKernelGGL((pspace_rows_kernel<G::NCH, G::NP>), dim3(us.blocks + is.blocks), dim3(256), lds_rows, st, us, is, n_pref, Alog, Ar, Cn, dp,
                        q.grams, G::KA, G::KS);
@@ -990,6 +998,7 @@ int launch_q_d(int d, int n_pref, const float* U, int64_t ldu, const int64_t* u_
                const float* pref_ws, int ppad, int dp, const int64_t* filt_off, const int32_t* filt_ids, int topn, void* scratch,
                int32_t* top_ids, float* top_scores, hipStream_t st, const char* name) {
   if (d == 64) return launch_q_p<16, SEG>(n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
+  if (d == 256) return launch_q_p<64, SEG>(n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
   if (d == 100) return launch_q_p<25, SEG>(n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
   return launch_q_p<32, SEG>(n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
 }
@@ -1030,7 +1039,7 @@ int eval_pass_pspace(const float* U, int64_t ldu, const int64_t* u_ids, int64_t 
                      const int32_t* item2ent, int64_t n_items, const float* pref_ws,
                      int ppad, int dp, int n_pref, int d, const int64_t* filt_off, const int32_t* filt_ids, int topn, void* scratch,
                      int32_t* top_ids, float* top_scores, hipStream_t st, const char* name, bool wide) {
-  if ((d != 64 && d != 100 && d != 128) || n_pref < 1 || n_pref > 32 || topn < 1 || topn > (wide ? TOPN_WIDE_MAX : TOPN_MAX) ||
+  if ((d != 64 && d != 100 && d != 128 && d != 256) || n_pref < 1 || n_pref > 32 || topn < 1 || topn > (wide ? TOPN_WIDE_MAX : TOPN_MAX) ||
       n_items >= (1ll << 31))
     return 1;
   if (!wide) return launch_q_d<1>(d, n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);

@@ -67,6 +67,9 @@ Option g_opts[] = {
                                                                             // (ops.eval_kg_ranks_transr), who otherwise take ktup_eval_kg_ranks_transr_fused where it is the default: the same ranks
     {"eval_wide_topn", "KTUP_EVAL_WIDE_TOPN", {env_int("KTUP_EVAL_WIDE_TOPN", -1)}},   // rec evaluation at 17 <= topn <= 64, read by the callers (ops.topk_sweep_for): 0: the batch walk stays, 1: the wide-list
                                                                             // sweep (ktup_eval_dot_topk_wide, ktup_eval_cfkg_topk_wide), -1: the sweep where the caller's measured default says so
+    {"eval_q256", "KTUP_EVAL_Q256", {env_int("KTUP_EVAL_Q256", -1)}},                 // TUP / KTUP rec evaluation at d = 256 (soft gate, squared L2), read by the callers (ops.pref_pass_covers): 1: the
+                                                                            // preference-space pass (ktup_eval_pref_topk / _wide), 0: the pair kernel's sweep, -1: the sweep for the bare ops wrappers (their
+                                                                            // pinned bits), the models' evaluate_topk by ops.PREF_Q256_DEFAULT.  No effect at any other width
 };
 Option* find(const char* name) {
   for (auto& o : g_opts)

@@ -849,49 +849,81 @@ def _eval_pref(U, I, E, pref, pref_norm, rel, norm, item2ent, u, l1, gumbel_mode
 
 
 @torch.no_grad()
-def eval_pref_topk(U, u, items, l1, topn, filt_off=None, filt_ids=None, with_scores=False):
+def eval_pref_topk(U, u, items, l1, topn, filt_off=None, filt_ids=None, with_scores=False, model_call=False):
     """Scores + filtered top-n of a whole evaluation pass in one sweep (ktup_eval_pref_topk): every user of `u` against the
     item tables of `items`, no (users x items) matrix.  Squared L2 at d in {64, 100, 128}: the preference-space pass on the matrix cores;
-    L1 and other widths: the pair kernel's arithmetic swept with the top-n in its epilogue (the per-batch scores' bits).  -> int32
+    L1 and other widths: the pair kernel's arithmetic swept with the top-n in its epilogue (the per-batch scores' bits).  d = 256 takes
+    the preference-space pass where option eval_q256 says so (pref_pass_covers; `model_call`: asked by a model's evaluate_topk, for
+    which -1 means PREF_Q256_DEFAULT) and keeps the pair kernel's sweep otherwise, and where the pass declines the call.  -> int32
     (len(u), topn) ids (-1 padded) [, scores], or None when no sweep covers the shape (topn > 16: eval_pref_topk_wide; very wide
     rows): keep eval_tup / eval_ktup + topk_filtered."""
-    return _eval_pref_topk('ktup_eval_pref_topk', TOPN_MAX, eval_pref_topk_hard, U, u, items, l1, topn, filt_off, filt_ids, with_scores)
+    return _eval_pref_topk('ktup_eval_pref_topk', TOPN_MAX, eval_pref_topk_hard, U, u, items, l1, topn, filt_off, filt_ids, with_scores,
+                           model_call)
 
 
 @torch.no_grad()
-def eval_pref_topk_wide(U, u, items, l1, topn, filt_off=None, filt_ids=None, with_scores=False):
+def eval_pref_topk_wide(U, u, items, l1, topn, filt_off=None, filt_ids=None, with_scores=False, model_call=False):
     """eval_pref_topk on the wide lists (ktup_eval_pref_topk_wide): the same arguments, scores and order for 1 <= topn <= 64.  L1,
     other widths and eval_mc = 0 go to eval_pref_topk_hard_wide as the narrow wrapper's go to eval_pref_topk_hard.  None for
     topn > 64, d > 256, P > 32 and where the library declines the shape."""
     return _eval_pref_topk('ktup_eval_pref_topk_wide', TOPN_WIDE_MAX, eval_pref_topk_hard_wide, U, u, items, l1, topn, filt_off, filt_ids,
-                           with_scores)
+                           with_scores, model_call)
 
 
-def pref_pass_covers(items, l1):
+# Is the preference-space pass the route of a model's evaluate_topk at d = 256 (soft gate, squared L2) when nobody says otherwise
+# (library option eval_q256 / KTUP_EVAL_Q256 = -1; 0: never, the pair kernel's sweep stays; 1: always, the bare wrappers included)?
+# The bare wrappers keep the sweep at -1 whatever this says: their bits at d = 256 are pinned to the matrix route's
+# (tests/test_hip_pref_wide_topn.py, tests/test_hip_eval.py).  The rule is PREF_WIDE_TOPN_DEFAULT's, on profiles/pref_q256_times.txt
+# (tools/pref_q256_time.py; DESIGN.md 6q): the pass is 2.3 - 4.0 x faster (gains of 0.9 - 1.1 ms per ml1m-size pass), but one of the
+# twelve comparisons held a single slow round whose spread (1.35 ms) exceeds its gain, so by the rule the pass stays opt-in.
+PREF_Q256_DEFAULT = False
+
+
+def pref_q256(model_call=False):
+    """Does a d = 256 soft-gate squared-L2 call take the preference-space pass?  model_call: the question of a model's evaluate_topk
+    (-1 = PREF_Q256_DEFAULT) rather than of a bare wrapper (-1 = no)."""
+    opt = L.get_option('eval_q256')
+    return opt > 0 or (opt < 0 and bool(model_call) and PREF_Q256_DEFAULT)
+
+
+def pref_pass_covers(items, l1, model_call=False):
     """Does the preference-space pass (soft gate) serve these item tables, or does the pair kernel's sweep?"""
-    return not l1 and items.d in (64, 100, 128) and bool(L.get_option('eval_mc'))
+    if l1 or not L.get_option('eval_mc'):
+        return False
+    if items.d == 256:
+        return items.P <= 32 and pref_q256(model_call)
+    return items.d in (64, 100, 128)
 
 
-def _eval_pref_topk(entry, topn_max, hard, U, u, items, l1, topn, filt_off, filt_ids, with_scores):
+def pref_route_key():
+    """The options the callers read to pick a TUP / KTUP / dot / CFKG evaluation route, for the key of a captured pass."""
+    return tuple(L.get_option(name) for name in ('eval_mc', 'eval_wide_topn', 'eval_q256'))
+
+
+def _eval_pref_topk(entry, topn_max, hard, U, u, items, l1, topn, filt_off, filt_ids, with_scores, model_call=False):
     U, u = _pad_users(U, u)
     dev = _dev(_table('user table', U))
     u = _ids('u_ids', u, dev)
     nq, d, P = u.numel(), items.d, items.P
     if not (0 < topn <= topn_max) or nq == 0 or d > 256:
         return None
-    if not pref_pass_covers(items, l1):
+    if not pref_pass_covers(items, l1, model_call):
         # no preference-space pass for this shape: the pair kernel's arithmetic with the top-n in its epilogue (or None: per-batch calls)
         return hard(U, u, items, l1, topn, GUMBEL_OFF, None, 0, 0, filt_off, filt_ids, with_scores)
     wide = topn_max > TOPN_MAX
     if wide and P > 32:
         return None
-    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
+    f_off, f_ids = _no_empty_filter(filt_off, filt_ids)
     I, E = items.I, items.E
     args = (_p(U), U.stride(0), _p(I), I.stride(0), _p(E), 0 if E is None else E.stride(0), _p(items.item2ent), _p(items.pws), P, d, _p(u),
-            nq, items.n_items, 0, _p(filt_off), _p(filt_ids), int(topn))
-    # (the wide pass may decline: a catalogue whose filter bits no longer fit the LDS beside the longer lists)
-    return _topn_sweep(entry, args, getattr(L.load(), entry + '_workspace_bytes')(d, P, nq, items.n_items, topn), nq, topn,
-                       dev, with_scores, may_decline=wide)
+            nq, items.n_items, 0, _p(f_off), _p(f_ids), int(topn))
+    # (the wide pass may decline: a catalogue whose filter bits no longer fit the LDS beside the longer lists; at d = 256 either form
+    #  may -- the tiles are larger --, and the call then gets what it gets without the option: the pair kernel's sweep)
+    got = _topn_sweep(entry, args, getattr(L.load(), entry + '_workspace_bytes')(d, P, nq, items.n_items, topn), nq, topn,
+                      dev, with_scores, may_decline=wide or d == 256)
+    if got is None and d == 256:
+        return hard(U, u, items, l1, topn, GUMBEL_OFF, None, 0, 0, filt_off, filt_ids, with_scores)
+    return got
 
 
 @torch.no_grad()

@@ -224,11 +224,13 @@ def _single_process():
 
 
 def model_graph_key(model):
-    """What a captured evaluation pass of `model` depends on besides the pass's own inputs: the addresses of its tables.  None for a
-    model whose pass draws noise (ST-Gumbel gate): a replay would repeat the captured stream position."""
+    """What a captured evaluation pass of `model` depends on besides the pass's own inputs: the addresses of its tables and the
+    options by which evaluate_topk picks its route (a graph replays the route it was captured on).  None for a model whose pass
+    draws noise (ST-Gumbel gate): a replay would repeat the captured stream position."""
     if getattr(model, 'use_st_gumbel', False):
         return None
-    return (id(model),) + tuple(p.data_ptr() for p in model.parameters())
+    from jTransUP.hip import ops
+    return (id(model),) + tuple(p.data_ptr() for p in model.parameters()) + ops.pref_route_key()
 
 
 def _rec_eval_fused(FLAGS, pass_fn, eval_iter, index, graph_key=None):

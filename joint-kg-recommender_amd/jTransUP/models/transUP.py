@@ -55,7 +55,8 @@ class TransUPModel(nn.Module, GradToggle, GateHelpers):
         """K15 + K17 for a whole evaluation pass in one sweep (this build): filtered top-n item ids of every user of `u_ids`
         without the (users x items) matrix.  The ST-Gumbel gate takes the hard gate's sweep (fresh Philox noise per pass, as `evaluate`
         draws it per batch); None when no fused pass applies (an unsupported width; 17 <= topn <= 64 where the wide sweep of the
-        call's route is neither the default nor asked for, ops.PREF_WIDE_TOPN_DEFAULT; topn > 64)."""
+        call's route is neither the default nor asked for, ops.PREF_WIDE_TOPN_DEFAULT; topn > 64).  Embedding size 256 with the soft gate
+        and squared L2: the preference-space pass or the pair kernel's sweep by option eval_q256 / ops.PREF_Q256_DEFAULT."""
         if self.use_st_gumbel:
             mode, uni, seed, off = self._gumbel.mode_and_stream(True, None, u_ids.numel() * items.n_items * items.P)
             sweep = ops.topk_sweep_for(topn, ops.eval_pref_topk_hard, ops.eval_pref_topk_hard_wide, 'pref_hard')
@@ -63,10 +64,10 @@ class TransUPModel(nn.Module, GradToggle, GateHelpers):
                 return None
             return sweep(self.user_embeddings.weight, u_ids, items, self.L1_flag, topn, mode, uni, seed, off, filt_off, filt_ids)
         sweep = ops.topk_sweep_for(topn, ops.eval_pref_topk, ops.eval_pref_topk_wide,
-                                   'pref_q' if ops.pref_pass_covers(items, self.L1_flag) else 'pref_soft')
+                                   'pref_q' if ops.pref_pass_covers(items, self.L1_flag, model_call=True) else 'pref_soft')
         if sweep is None:
             return None
-        return sweep(self.user_embeddings.weight, u_ids, items, self.L1_flag, topn, filt_off, filt_ids)
+        return sweep(self.user_embeddings.weight, u_ids, items, self.L1_flag, topn, filt_off, filt_ids, model_call=True)
 
     def prepare_items(self):
         """Item side of `evaluate` (the item projections of the preference gate), to share between the batches of a pass."""

@@ -1,5 +1,7 @@
 """Small fixed workloads for rocprofv3 counter passes (run under `rocprofv3 --kernel-trace --pmc ... -- python tools/pmc_workloads.py <name>`):
     eval_pass   the fused all-item evaluation sweep at ml1m shape (ktup_eval_pref_topk), 5 sweeps
+    q256_pass   the same at embedding size 256 on both routes: 5 passes each of the preference-space pass (option eval_q256 = 1) and of
+                the pair kernel's sweep (0) at topn 10, then 5 of the wide pass at topn 50
     train_step  the three-launch B=512 joint training step, 20 rec + 20 kg steps
     fed_step    the device-fed B=512 joint step (-device_sampling): feed launch + step + clip/optimizer, ten-step graphs
     seg_bwd     the large-batch backwards by sorted segments: TransE (307,200 triples) and KTUP (716,800 pairs), 5 each
@@ -19,18 +21,27 @@ import torch
 import bench as B
 
 
-def eval_pass(dev):
+def eval_pass(dev, d=None, route=None):
     from jTransUP.models import jTransUP as jt
     torch.manual_seed(3)
     i_map = {i: i for i in range(B.NI)}
     new_map = {i: ((i * 4) % B.NE if i < B.ALIGNED else -1, i) for i in range(B.NI)}
-    m = jt.jTransUPModel(False, B.D, B.NU, B.NI, B.NE, B.NR, i_map, new_map, False, False)
+    m = jt.jTransUPModel(False, d or B.D, B.NU, B.NI, B.NE, B.NR, i_map, new_map, False, False)
     m.eval(); m.disable_grad()
     u = torch.arange(B.NU, device=dev)
     gen = torch.Generator().manual_seed(1)
     f_off = (torch.arange(B.NU + 1) * 165).to(dev)
     f_ids = torch.randint(0, B.NI, (B.NU * 165,), generator=gen).to(dev, torch.int32)
     items = m.prepare_items()
+    if route is not None:
+        from jTransUP.hip import lib as L
+        for q, topn in route:
+            L.set_option('eval_q256', q)
+            L.set_option('eval_wide_topn', 1)
+            for _ in range(5):
+                m.evaluate_topk(u, items, topn, f_off, f_ids)
+        torch.cuda.synchronize()
+        return
     for _ in range(5):
         m.evaluate_topk(u, items, 10, f_off, f_ids)
     torch.cuda.synchronize()
@@ -162,4 +173,4 @@ def soft_l1_pass(dev):
 
 
 if __name__ == '__main__':
-    {'soft_l1_pass': soft_l1_pass, 'kg_pass': kg_pass, 'kg_pass_e': lambda d: kg_pass(d, True), 'kg_pass_e_l1': lambda d: kg_pass(d, True, True), 'kg_pass_l1': lambda d: kg_pass(d, False, True), 'hard_pass': hard_pass, 'kg_rank': kg_rank, 'eval_pass': eval_pass, 'train_step': train_step, 'fed_step': fed_step, 'seg_bwd': seg_bwd}[sys.argv[1]](torch.device('cuda'))
+    {'soft_l1_pass': soft_l1_pass, 'kg_pass': kg_pass, 'kg_pass_e': lambda d: kg_pass(d, True), 'kg_pass_e_l1': lambda d: kg_pass(d, True, True), 'kg_pass_l1': lambda d: kg_pass(d, False, True), 'hard_pass': hard_pass, 'kg_rank': kg_rank, 'eval_pass': eval_pass, 'q256_pass': lambda d: eval_pass(d, 256, ((1, 10), (0, 10), (1, 50))), 'train_step': train_step, 'fed_step': fed_step, 'seg_bwd': seg_bwd}[sys.argv[1]](torch.device('cuda'))
