@@ -382,6 +382,29 @@ int ktup_eval_kg_ranks_fused(int model, const float* E, int64_t lde, const float
                              int descending, const int64_t* filt_off, const int32_t* filt_ids, int64_t n_filt,
                              const int64_t* gold_off, const int32_t* gold_ids, int64_t n_gold, int64_t max_golds, int32_t* ranks,
                              void* ws, void* stream);
+/* Link prediction as LISTS (csrc/ktup_kg_topn.hip): the topn unfiltered candidates with the smallest distance for each of the nq keys
+ * (q[i], r[i]) -- "which tails complete (h, r, ?)" (head = 0) or "which heads complete (?, r, t)" (head = 1) -- with the scores of
+ * evaluateTail / evaluateHead (transE.py:65-105, transH.py:73-121), in ONE sweep that never writes the (keys x candidates) matrix
+ * (the sweep of csrc/ktup_sweep_pass.h, as ktup_eval_cfkg_topk).  model: KTUP_KG_TRANSE (Nrm ignored) or KTUP_KG_TRANSH (w = Nrm[r]):
+ *     TransE   c = E[q] + R[r] (tail) or E[q] - R[r] (head),            z = c - e
+ *     TransH   c = (E[q] - (w.E[q]) w) + R[r]   or   ... - R[r],        z = c - e + (w.e) w       (|w| = 1 is not assumed)
+ * distance = sum |z_k| (l1) or sum z_k^2, e = row j of C (n_cand rows; the returned ids and the filter ids are row numbers j).
+ * Squared L2 runs on the fp32 matrix cores as |c|^2 - 2 c.e + |e|^2 [+ (w.e) (2 w.c - (2 - |w|^2) (w.e))], L1 on the VALU.  The list is
+ * ordered by the fp32 scores the pass itself computes (ascending, ties -> lower j; no fp64 resolve as under option kg_exact): the
+ * order of ktup_eval_trans{e,h}_scores + ktup_eval_topk_filtered with descending = 0, the scores up to fp32 rounding, not bit for bit.
+ * top_ids [nq][topn] is padded with -1, top_scores [nq][topn] (may be NULL) with 0.0.  1 <= topn <= 64 (the list is one, two or four
+ * 16-key segments: up to 16, 32, 64); a score is the same bits at every topn and every nsplit (candidate splits; 0 = chosen here).
+ * Any d <= 256, pitched or unaligned rows (element-wise stage loads where d % 4 != 0 or C is not 16-byte aligned rows).  filt_off
+ * (nq + 1 absolute offsets) / filt_ids: given together or both NULL; ids outside [0, n_cand) filter nothing.  n_rel = rows of R (and
+ * Nrm).  KTUP_ERR_UNSUPPORTED (and _supported 0, workspace size 0): another model, topn > 64, d > 256, n_cand >= 2^31.  Pointers and
+ * sizes are checked on the host before any launch.  `ws`: ktup_eval_kg_topk_workspace_bytes bytes for the same arguments, 16-byte
+ * aligned.                                                                                                                      */
+int ktup_eval_kg_topk_supported(int model, int d, int l1, int topn);
+size_t ktup_eval_kg_topk_workspace_bytes(int model, int d, int64_t nq, int64_t n_cand, int64_t n_rel, int topn, int nsplit);
+int ktup_eval_kg_topk(int model, const float* E, int64_t lde, const float* R, int64_t ldr, const float* Nrm, int64_t ldn,
+                      int64_t n_rel, int d, const float* C, int64_t ldc, int64_t n_cand, const int64_t* q, const int64_t* r,
+                      int64_t nq, int l1, int head, const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit,
+                      int32_t* top_ids, float* top_scores, void* ws, void* stream);
 /* TransR (transR.py:80-128): the same pass over the entity table; ents_ws = ktup_eval_transr_prepare's output for these tables
  * (NULL: the entity side is recomputed per chunk).  The score matrix of a chunk is double-buffered and K18 of chunk c runs on a
  * library-owned second stream beside the score kernel of chunk c + 1 (not during graph capture).                              */

@@ -691,6 +691,66 @@ def eval_kg_ranks(E, R, N, q, r, l1, head, descending, gold_off, gold_ids, filt_
     return ranks
 
 
+@torch.no_grad()
+def eval_kg_topk(E, R, N, q, r, l1, head, topn, filt_off=None, filt_ids=None, candidates=None, with_scores=False, nsplit=0):
+    """Link prediction as lists in one sweep (ktup_eval_kg_topk): for every key (q[i], r[i]) the `topn` unfiltered candidate rows with
+    the smallest TransE (N is None) or TransH distance -- the tails of (q, r, ?) or, with `head`, the heads of (?, r, q) -- without
+    the (keys x candidates) matrix; the order of eval_transe / eval_transh + topk_filtered(descending=False), the scores up to fp32
+    rounding.  candidates: the table the candidates are rows of (None: E); filter ids and the returned ids are its row numbers.
+    -> int32 (len(q), topn) ids (-1 padded) [, fp32 scores (0.0 padded)], or None where the entry point declines (topn > 64, d > 256,
+    no keys or no candidates): keep the score matrix + topk_filtered."""
+    dev = _dev(_table('entity table', E)); _table('relation table', R)
+    if N is not None:
+        _table('norm table', N)
+    C = E if candidates is None else _table('candidate table', candidates)
+    if any(t.device != dev or t.shape[1] != E.shape[1] for t in (R, C) + (() if N is None else (N,))):
+        raise L.KtupError('entity, relation, norm and candidate tables must share the device and the embedding size')
+    nq = q.numel(); q = _ids('q', q, dev); r = _ids('r', r, dev, nq)
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
+    if filt_off is not None and filt_off.numel() != nq + 1:
+        raise L.KtupError('eval_kg_topk: CSR offsets need len(q) + 1 entries')
+    model, n_rel = (KG_TRANSE, R.shape[0]) if N is None else (KG_TRANSH, min(R.shape[0], N.shape[0]))
+    d, nc, topn, nsplit = E.shape[1], C.shape[0], int(topn), int(nsplit)
+    lib = L.load()
+    if nq == 0 or nc == 0 or n_rel == 0 or not lib.ktup_eval_kg_topk_supported(model, d, int(bool(l1)), topn):
+        return None
+    args = (model, _p(E), E.stride(0), _p(R), R.stride(0), _p(N), 0 if N is None else N.stride(0), n_rel, d, _p(C), C.stride(0), nc, _p(q),
+            _p(r), nq, int(bool(l1)), int(bool(head)), _p(filt_off), _p(filt_ids), topn, nsplit)
+    return _topn_sweep('ktup_eval_kg_topk', args, lib.ktup_eval_kg_topk_workspace_bytes(model, d, nq, nc, n_rel, topn, nsplit), nq, topn, dev,
+                       with_scores)
+
+
+KG_TOPK_ROUTE = [None]           # the route the last predict_kg_entities call took
+
+
+@torch.no_grad()
+def predict_kg_entities(E, R, N, q, r, l1, head, topn, filt_off=None, filt_ids=None, candidates=None, with_scores=False, chunk=512):
+    """eval_kg_topk wherever the entry point covers the shape; elsewhere (topn > 64, d > 256) what there was before it: the
+    (keys x candidates) score matrix `chunk` keys at a time (eval_transe / eval_transh) through topk_filtered(descending=False).
+    -> as eval_kg_topk, never None."""
+    got = eval_kg_topk(E, R, N, q, r, l1, head, topn, filt_off, filt_ids, candidates, with_scores)
+    if got is not None:
+        KG_TOPK_ROUTE[0] = 'no score matrix (ktup_eval_kg_topk)'
+        return got
+    KG_TOPK_ROUTE[0] = 'chunked score matrix (ktup_eval_topk_filtered)'
+    dev = E.device
+    nq, topn = q.numel(), int(topn)
+    q = _ids('q', q, dev); r = _ids('r', r, dev, nq)
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
+    ids = [torch.empty(0, topn, dtype=torch.int32, device=dev)]
+    scs = [torch.empty(0, topn, dtype=torch.float32, device=dev)]
+    for lo in range(0, nq, max(1, int(chunk))):
+        hi = min(nq, lo + max(1, int(chunk)))
+        mat = eval_transe(E, R, q[lo:hi], r[lo:hi], l1, head, candidates) if N is None else \
+            eval_transh(E, R, N, q[lo:hi], r[lo:hi], l1, head, candidates)
+        off = None if filt_off is None else filt_off[lo:hi + 1]           # (absolute offsets into the whole id array)
+        top = topk_filtered(mat, False, topn, off, filt_ids, with_scores=with_scores)
+        ids.append(top[0] if with_scores else top)
+        if with_scores:
+            scs.append(top[1])
+    return (torch.cat(ids), torch.cat(scs)) if with_scores else torch.cat(ids)
+
+
 # l1 -> whether the TransR / CKE pass without the score matrix is the default for that distance: only where its median gain over the
 # chunked route exceeded the larger spread in both runs of tools/transr_pass_time.py (profiles/transr_pass_times.txt)
 TRANSR_FUSED_DEFAULT = {False: True, True: True}

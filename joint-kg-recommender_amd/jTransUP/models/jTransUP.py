@@ -156,6 +156,15 @@ class jTransUPModel(nn.Module, GradToggle, GateHelpers):
         return ops.eval_kg_ranks(self.ent_embeddings.weight, self.rel_embeddings.weight, self.norm_embeddings.weight, q, r, self.L1_flag,
                                  head, descending, gold_off, gold_ids, filt_off, filt_ids, candidates=self._all_entities(all_e_ids))
 
+    def predict_entities(self, q, r, head, topn, filt_off=None, filt_ids=None, with_scores=False, all_e_ids=None):
+        """The `topn` unfiltered candidates nearest to every key on the TransH side -- tails of (q, r, ?) or, with `head`, heads of
+        (?, r, q) -- ascending distance, ties -> lower id: int32 (len(q), topn), -1 padded [, their scores].  The candidates are those of
+        rank_entities (all_e_ids under shared embeddings, else every row including the pad row); ids are candidate row numbers.  One
+        sweep without the score matrix (ops.eval_kg_topk) up to topn 64 and d 256, the chunked matrix + ops.topk_filtered beyond."""
+        return ops.predict_kg_entities(self.ent_embeddings.weight, self.rel_embeddings.weight, self.norm_embeddings.weight, q, r,
+                                       self.L1_flag, head, topn, filt_off, filt_ids, candidates=self._all_entities(all_e_ids),
+                                       with_scores=with_scores)
+
     def getPreferences(self, u_e, i_e, use_st_gumbel=False):
         """jTransUP.py:250-260 on already-gathered embeddings (reporting path only)."""
         A = self.pref_embeddings.weight + self.rel_embeddings.weight
