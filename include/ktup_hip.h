@@ -405,6 +405,37 @@ int ktup_eval_kg_topk(int model, const float* E, int64_t lde, const float* R, in
                       int64_t n_rel, int d, const float* C, int64_t ldc, int64_t n_cand, const int64_t* q, const int64_t* r,
                       int64_t nq, int l1, int head, const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit,
                       int32_t* top_ids, float* top_scores, void* ws, void* stream);
+/* The same lists for the models whose CANDIDATE side depends on the key's relation (csrc/ktup_kg_topn_rel.hip), with the scores of
+ * evaluateTail / evaluateHead, sgn = +1 (head = 0) or -1 (head = 1); the candidates are the rows e of the entity table E itself:
+ *     KTUP_KG_TRANSR  (transR.py:80-128, CKE.py:155-203; ktup_eval_transr_scores)    A = M: n_rel rows of d * d floats, lda >= d * d; B NULL
+ *                     c = M_r E[q] + sgn R[r],                       z = c - M_r e
+ *     KTUP_KG_TRANSD  (transD.py:78-134; ktup_eval_transd_scores)                    A = Ep: entity rows, B = Rp: relation rows
+ *                     a = Ep[q], b = Rp[r], c = E[q] + (E[q].a) b + sgn R[r],   z = c - e - (e.a) b
+ *                     (every candidate is projected with the QUERY's row a; transD.py:127 names an undefined t_proj_expand, the
+ *                     h_proj_expand computed two lines above is what runs, as in ktup_eval_transd_scores)
+ * distance = sum |z_k| (l1) or sum z_k^2; ascending in the fp32 scores the pass computes, ties -> lower entity row, no fp64 resolve;
+ * top_ids / top_scores, topn, nsplit, filt_off / filt_ids (ids outside [0, n_ent) filter nothing) as in ktup_eval_kg_topk; a score is
+ * the same bits at every topn, every nsplit and every order of the keys.  The sweep of csrc/ktup_sweep_pass.h stages one stream of
+ * candidate rows per 64 keys, so the keys are bucketed by relation on the device into whole 64-key blocks (at most
+ * nq / 64 + min(n_rel, nq) of them: what the workspace and the grid are sized for).  TransR: the entity table is projected once per
+ * call into the workspace ([n_rel][n_ent][round4(d)] floats, and |M_r e|^2 beside it) and a block runs TransE's arithmetic against
+ * its relation's slice.  TransD: an n_rel x n_ent table of b.e is built once per call (squared L2), s = a.e is a second MFMA chain:
+ * |c|^2 - 2 c.e + |e|^2 - 2 s (b.c - b.e) + s^2 |b|^2; L1: sum |c_k - e_k - s b_k| on the VALU.  Any d <= 256, pitched or unaligned E.
+ * KTUP_ERR_UNSUPPORTED: another model, topn > 64, d > 256 (for these _supported is 0 and the workspace size 0), n_ent >= 2^31,
+ * n_rel > 16384.  KTUP_ERR_INVALID_ARG (the argument is named): null tables, ids, outputs or workspace, B null under KTUP_KG_TRANSD,
+ * sizes below 1, pitches below d (lda below d * d under KTUP_KG_TRANSR), filt_off without filt_ids or the reverse, a workspace off a
+ * 16-byte boundary.  All of it is checked on the host before any launch; nq = 0 returns KTUP_OK and launches nothing.  `ws`:
+ * ktup_eval_kg_topk_rel_workspace_bytes bytes for the same arguments.                                                           */
+#define KTUP_KG_TRANSR 2
+#define KTUP_KG_TRANSD 3
+int ktup_eval_kg_topk_rel_supported(int model, int d, int l1, int topn);
+size_t ktup_eval_kg_topk_rel_workspace_bytes(int model, int d, int64_t nq, int64_t n_ent, int64_t n_rel, int topn, int nsplit);
+int ktup_eval_kg_topk_rel(int model, const float* E, int64_t lde, const float* R, int64_t ldr,
+                          const float* A, int64_t lda,   /* TransR: M (n_rel rows of d*d, lda >= d*d); TransD: Ep (entity rows) */
+                          const float* B, int64_t ldb,   /* TransR: NULL; TransD: Rp (relation rows) */
+                          int64_t n_rel, int d, int64_t n_ent, const int64_t* q, const int64_t* r, int64_t nq, int l1, int head,
+                          const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit,
+                          int32_t* top_ids, float* top_scores, void* ws, void* stream);
 /* TransR (transR.py:80-128): the same pass over the entity table; ents_ws = ktup_eval_transr_prepare's output for these tables
  * (NULL: the entity side is recomputed per chunk).  The score matrix of a chunk is double-buffered and K18 of chunk c runs on a
  * library-owned second stream beside the score kernel of chunk c + 1 (not during graph capture).                              */

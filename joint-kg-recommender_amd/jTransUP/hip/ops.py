@@ -732,8 +732,62 @@ def predict_kg_entities(E, R, N, q, r, l1, head, topn, filt_off=None, filt_ids=N
     if got is not None:
         KG_TOPK_ROUTE[0] = 'no score matrix (ktup_eval_kg_topk)'
         return got
-    KG_TOPK_ROUTE[0] = 'chunked score matrix (ktup_eval_topk_filtered)'
+    return _predict_chunked(lambda qc, rc: eval_transe(E, R, qc, rc, l1, head, candidates) if N is None else
+                            eval_transh(E, R, N, qc, rc, l1, head, candidates), E.device, q, r, topn, filt_off, filt_ids, with_scores, chunk)
+
+
+KG_TRANSR, KG_TRANSD = 2, 3
+
+
+def _eval_kg_topk_rel(who, model, E, R, A, B, n_rel, q, r, l1, head, topn, filt_off, filt_ids, with_scores, nsplit):
+    """The shared tail of eval_kg_topk_transr / eval_kg_topk_transd (ktup_eval_kg_topk_rel); the tables are checked by the callers."""
     dev = E.device
+    nq = q.numel(); q = _ids('q', q, dev); r = _ids('r', r, dev, nq)
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
+    if filt_off is not None and filt_off.numel() != nq + 1:
+        raise L.KtupError('%s: CSR offsets need len(q) + 1 entries' % who)
+    d, ne, topn, nsplit = E.shape[1], E.shape[0], int(topn), int(nsplit)
+    lib = L.load()
+    if nq == 0 or ne == 0 or n_rel == 0 or not lib.ktup_eval_kg_topk_rel_supported(model, d, int(bool(l1)), topn):
+        return None
+    ws_bytes = lib.ktup_eval_kg_topk_rel_workspace_bytes(model, d, nq, ne, n_rel, topn, nsplit)
+    if ws_bytes == 0:                                                      # more than 16384 relations: declined before any workspace exists
+        return None
+    args = (model, _p(E), E.stride(0), _p(R), R.stride(0), _p(A), A.stride(0), _p(B), 0 if B is None else B.stride(0), n_rel, d, ne, _p(q),
+            _p(r), nq, int(bool(l1)), int(bool(head)), _p(filt_off), _p(filt_ids), topn, nsplit)
+    return _topn_sweep('ktup_eval_kg_topk_rel', args, ws_bytes, nq, topn, dev, with_scores)
+
+
+@torch.no_grad()
+def eval_kg_topk_transr(E, R, M, q, r, l1, head, topn, filt_off=None, filt_ids=None, with_scores=False, nsplit=0):
+    """Link prediction as lists in one sweep for TransR / CKE (ktup_eval_kg_topk_rel): for every key (q[i], r[i]) the `topn`
+    unfiltered rows e of the entity table with the smallest distance of c - M_r e, c = M_r E[q] +- R[r] (transR.py:80-128) -- without
+    the (keys x entities) matrix; the order of eval_transr + topk_filtered(descending=False), the scores up to fp32 rounding.  The
+    keys are bucketed by relation on the device; the entity table is projected once per call.
+    -> int32 (len(q), topn) ids (-1 padded) [, fp32 scores (0.0 padded)], or None where the entry point declines (topn > 64, d > 256,
+    more than 16384 relations, no keys or no entities): keep the score matrix + topk_filtered."""
+    dev = _dev(_table('entity table', E)); _table('relation table', R); _table('projection table', M)
+    if R.device != dev or M.device != dev or R.shape[1] != E.shape[1] or M.shape[1] != E.shape[1] * E.shape[1]:
+        raise L.KtupError('entity, relation and projection tables must share the device; rows of d, d and d * d floats')
+    return _eval_kg_topk_rel('eval_kg_topk_transr', KG_TRANSR, E, R, M, None, min(R.shape[0], M.shape[0]), q, r, l1, head, topn, filt_off,
+                             filt_ids, with_scores, nsplit)
+
+
+@torch.no_grad()
+def eval_kg_topk_transd(E, R, Ep, Rp, q, r, l1, head, topn, filt_off=None, filt_ids=None, with_scores=False, nsplit=0):
+    """eval_kg_topk_transr for TransD (transD.py:78-134): the distance of c - e - (e . a) b with a = Ep[q] the QUERY's projection row,
+    b = Rp[r], c = E[q] + (E[q] . a) b +- R[r]; the order of eval_transd + topk_filtered(descending=False).  -> as eval_kg_topk_transr."""
+    dev = _dev(_table('entity table', E)); _table('relation table', R)
+    _table('entity projection table', Ep); _table('relation projection table', Rp)
+    if any(t.device != dev or t.shape[1] != E.shape[1] for t in (R, Ep, Rp)) or Ep.shape[0] < E.shape[0]:
+        raise L.KtupError('entity, relation and projection tables must share the device and the embedding size')
+    return _eval_kg_topk_rel('eval_kg_topk_transd', KG_TRANSD, E, R, Ep, Rp, min(R.shape[0], Rp.shape[0]), q, r, l1, head, topn, filt_off,
+                             filt_ids, with_scores, nsplit)
+
+
+def _predict_chunked(score_chunk, dev, q, r, topn, filt_off, filt_ids, with_scores, chunk):
+    """The (keys x entities) score matrix `chunk` keys at a time through topk_filtered(descending=False)."""
+    KG_TOPK_ROUTE[0] = 'chunked score matrix (ktup_eval_topk_filtered)'
     nq, topn = q.numel(), int(topn)
     q = _ids('q', q, dev); r = _ids('r', r, dev, nq)
     filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
@@ -741,14 +795,36 @@ def predict_kg_entities(E, R, N, q, r, l1, head, topn, filt_off=None, filt_ids=N
     scs = [torch.empty(0, topn, dtype=torch.float32, device=dev)]
     for lo in range(0, nq, max(1, int(chunk))):
         hi = min(nq, lo + max(1, int(chunk)))
-        mat = eval_transe(E, R, q[lo:hi], r[lo:hi], l1, head, candidates) if N is None else \
-            eval_transh(E, R, N, q[lo:hi], r[lo:hi], l1, head, candidates)
-        off = None if filt_off is None else filt_off[lo:hi + 1]           # (absolute offsets into the whole id array)
-        top = topk_filtered(mat, False, topn, off, filt_ids, with_scores=with_scores)
+        off = None if filt_off is None else filt_off[lo:hi + 1]               # (absolute offsets into the whole id array)
+        top = topk_filtered(score_chunk(q[lo:hi], r[lo:hi]), False, topn, off, filt_ids, with_scores=with_scores)
         ids.append(top[0] if with_scores else top)
         if with_scores:
             scs.append(top[1])
     return (torch.cat(ids), torch.cat(scs)) if with_scores else torch.cat(ids)
+
+
+@torch.no_grad()
+def predict_kg_entities_transr(E, R, M, q, r, l1, head, topn, filt_off=None, filt_ids=None, with_scores=False, chunk=512):
+    """eval_kg_topk_transr wherever the entry point covers the shape; elsewhere the score matrix `chunk` keys at a time (eval_transr
+    against the entity side prepared once) through topk_filtered(descending=False).  -> as eval_kg_topk_transr, never None."""
+    got = eval_kg_topk_transr(E, R, M, q, r, l1, head, topn, filt_off, filt_ids, with_scores)
+    if got is not None:
+        KG_TOPK_ROUTE[0] = 'no score matrix (ktup_eval_kg_topk_rel)'
+        return got
+    ents = eval_transr_entities(E, M, R.shape[0], l1) if q.numel() and E.shape[0] else None
+    return _predict_chunked(lambda qc, rc: eval_transr(E, R, M, qc, rc, l1, head, ents=ents), E.device, q, r, topn, filt_off, filt_ids,
+                            with_scores, chunk)
+
+
+@torch.no_grad()
+def predict_kg_entities_transd(E, R, Ep, Rp, q, r, l1, head, topn, filt_off=None, filt_ids=None, with_scores=False, chunk=512):
+    """predict_kg_entities_transr for TransD (eval_kg_topk_transd, else eval_transd in chunks)."""
+    got = eval_kg_topk_transd(E, R, Ep, Rp, q, r, l1, head, topn, filt_off, filt_ids, with_scores)
+    if got is not None:
+        KG_TOPK_ROUTE[0] = 'no score matrix (ktup_eval_kg_topk_rel)'
+        return got
+    return _predict_chunked(lambda qc, rc: eval_transd(E, R, Ep, Rp, qc, rc, l1, head), E.device, q, r, topn, filt_off, filt_ids,
+                            with_scores, chunk)
 
 
 # l1 -> whether the TransR / CKE pass without the score matrix is the default for that distance: only where its median gain over the

@@ -96,6 +96,14 @@ class CKE(nn.Module, GradToggle):
         return ops.eval_kg_ranks_transr(self.ent_embeddings.weight, self.rel_embeddings.weight, self.proj_embeddings.weight, q, r,
                                         self.L1_flag, head, descending, gold_off, gold_ids, filt_off, filt_ids, ents=ents)
 
+    def predict_entities(self, q, r, head, topn, filt_off=None, filt_ids=None, with_scores=False, all_e_ids=None):
+        """The `topn` unfiltered entity rows nearest to every key on the TransR side -- tails of (q, r, ?) or, with `head`, heads of
+        (?, r, q) -- ascending distance, ties -> lower id: int32 (len(q), topn), -1 padded [, their scores], over the entity table
+        INCLUDING the pad row like rank_entities (all_e_ids is ignored, as there).  One sweep without the score matrix
+        (ops.eval_kg_topk_transr) up to topn 64 and d 256, the chunked matrix + ops.topk_filtered beyond."""
+        return ops.predict_kg_entities_transr(self.ent_embeddings.weight, self.rel_embeddings.weight, self.proj_embeddings.weight, q, r,
+                                              self.L1_flag, head, topn, filt_off, filt_ids, with_scores=with_scores)
+
     def evaluateHead(self, t, r, all_e_ids=None, ents=None):
         """CKE.py:155-178 over the entity table INCLUDING the pad row."""
         return ops.eval_transr(self.ent_embeddings.weight, self.rel_embeddings.weight, self.proj_embeddings.weight, t, r, self.L1_flag,

@@ -89,3 +89,11 @@ class coFM(nn.Module, GradToggle):
         """A whole evaluateHead / evaluateTail pass + the filtered gold ranks (utils/misc.py:125-146) in one call."""
         return ops.eval_kg_ranks(self.ent_embeddings.weight, self.rel_embeddings.weight, None, q, r, self.L1_flag, head, descending,
                                  gold_off, gold_ids, filt_off, filt_ids, candidates=self._cand(all_e_ids))
+
+    def predict_entities(self, q, r, head, topn, filt_off=None, filt_ids=None, with_scores=False, all_e_ids=None):
+        """The `topn` unfiltered candidates nearest to every key -- tails of (q, r, ?) or, with `head`, heads of (?, r, q) -- ascending
+        distance, ties -> lower id: int32 (len(q), topn), -1 padded [, their scores].  The KG score is TransE's and the candidates are
+        those of rank_entities; one sweep without the score matrix (ops.eval_kg_topk) up to topn 64 and d 256, the chunked matrix +
+        ops.topk_filtered beyond."""
+        return ops.predict_kg_entities(self.ent_embeddings.weight, self.rel_embeddings.weight, None, q, r, self.L1_flag, head, topn,
+                                       filt_off, filt_ids, candidates=self._cand(all_e_ids), with_scores=with_scores)

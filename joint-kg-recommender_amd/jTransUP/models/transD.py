@@ -60,5 +60,12 @@ class TransDModel(nn.Module, GradToggle):
         E, R, Ep, Rp = self._tables()
         return ops.eval_kg_ranks_transd(E, R, Ep, Rp, q, r, self.L1_flag, head, descending, gold_off, gold_ids, filt_off, filt_ids)
 
+    def predict_entities(self, q, r, head, topn, filt_off=None, filt_ids=None, with_scores=False):
+        """The `topn` unfiltered entities nearest to every key -- tails of (q, r, ?) or, with `head`, heads of (?, r, q) -- ascending
+        distance, ties -> lower id: int32 (len(q), topn), -1 padded [, their scores].  One sweep without the score matrix
+        (ops.eval_kg_topk_transd) up to topn 64 and d 256, the chunked matrix + ops.topk_filtered beyond."""
+        E, R, Ep, Rp = self._tables()
+        return ops.predict_kg_entities_transd(E, R, Ep, Rp, q, r, self.L1_flag, head, topn, filt_off, filt_ids, with_scores=with_scores)
+
 
 TransHModel = TransDModel      # the reference's name for this class (transD.py:17)

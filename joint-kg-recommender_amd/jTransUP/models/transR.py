@@ -57,3 +57,10 @@ class TransRModel(nn.Module, GradToggle):
         keys under the C ABI, the rank kernel of a chunk beside the score kernel of the next."""
         E, R, M = self._tables()
         return ops.eval_kg_ranks_transr(E, R, M, q, r, self.L1_flag, head, descending, gold_off, gold_ids, filt_off, filt_ids, ents=ents)
+
+    def predict_entities(self, q, r, head, topn, filt_off=None, filt_ids=None, with_scores=False):
+        """The `topn` unfiltered entities nearest to every key -- tails of (q, r, ?) or, with `head`, heads of (?, r, q) -- ascending
+        distance, ties -> lower id: int32 (len(q), topn), -1 padded [, their scores].  One sweep without the score matrix
+        (ops.eval_kg_topk_transr) up to topn 64 and d 256, the chunked matrix + ops.topk_filtered beyond."""
+        E, R, M = self._tables()
+        return ops.predict_kg_entities_transr(E, R, M, q, r, self.L1_flag, head, topn, filt_off, filt_ids, with_scores=with_scores)
