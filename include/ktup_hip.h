@@ -1108,6 +1108,44 @@ int ktup_eval_cfkg_topk_wide(const float* U, int64_t ldu, const float* R, int64_
                              const int64_t* filt_off, const int32_t* filt_ids, int topn, int nsplit, int32_t* top_ids,
                              float* top_scores, void* ws, void* stream);
 
+/* =================================================================== gold ranks of a whole rec evaluation pass (csrc/ktup_rank_pass.hip)
+ * Where every held-out item stands -- what mean rank, MRR and AUC need -- in one sweep that never writes the (users x candidates)
+ * matrix: the counterpart of ktup_eval_kg_ranks_fused on the rec side.  Semantics: ktup_eval_gold_ranks applied to the scores of
+ * ktup_eval_dot_topk / ktup_eval_cfkg_topk (every argument those passes share has their meaning), that is
+ *     ranks[e] = #{candidates of the user ordered before gold entry e that are neither in the user's filter list nor among its golds}
+ * for every entry e of the CSR gold_off[nq + 1] (ABSOLUTE offsets, per user of u_ids) / gold_ids[n_gold]; a user may have no entry,
+ * an id may occur twice in a list (both entries get the same rank).  The order is the list pass's key order -- dot: descending
+ * score, ties -> lower id; CFKG: ascending distance, ties -> lower j -- on the list pass's own score BITS (one copy of the scorer
+ * code, csrc/ktup_sweep_scorers.h), so a gold the list pass shows at place p has rank p - (golds listed before it).
+ * ranks[e] = -1: the gold id is in the user's own filter list, outside [0, n), or (CFKG) names a candidate without an entity row.
+ * A rank is a sum of integer counts: the same integer at every nsplit and every order of u_ids (duplicates allowed); no float atomics.
+ *
+ * block_golds (host side, as max_golds of ktup_eval_kg_ranks_fused): the largest number of gold entries of a 64-user block,
+ *     max over b of gold_off[min(nq, 64 b + 64)] - gold_off[64 b].
+ * The gold keys and counters of a block live in the LDS beside the stages: at most KTUP_RANK_BLOCK_GOLDS entries per block at
+ * d <= 128 and KTUP_RANK_BLOCK_GOLDS_WIDE at 128 < d <= 256 (an ml1m-size test split has about 1,100).  Beyond that the entry point
+ * declines, it never truncates.  (A block that holds more entries than the caller announced is not ranked at all: all -1.)
+ *
+ * Any 1 <= d <= 256, any pitches (rows that are not 16-byte aligned or d % 4 != 0 are loaded element by element), n < 2^31.
+ * KTUP_ERR_UNSUPPORTED (and _supported 0, workspace size 0): d > 256, n >= 2^31, block_golds above the cap.  nq == 0 or n_gold == 0
+ * is KTUP_OK and launches nothing.  Null or short arguments are KTUP_ERR_INVALID_ARG before any launch.  nsplit as in the list
+ * passes (0 = chosen by the library, at most 32).  `ws`: _workspace_bytes for the same arguments, 16-byte aligned.  No host
+ * synchronisation: the call can be captured into a graph.                                                                       */
+#define KTUP_RANK_BLOCK_GOLDS 3072
+#define KTUP_RANK_BLOCK_GOLDS_WIDE 2048
+int ktup_eval_dot_ranks_supported(int d, int64_t n_items, int64_t block_golds);
+size_t ktup_eval_dot_ranks_workspace_bytes(int d, int64_t nq, int64_t n_items, int64_t n_gold, int64_t block_golds);
+int ktup_eval_dot_ranks(const float* U, int64_t ldu, const float* I, int64_t ldi, int d, const int64_t* u_ids, int64_t nq,
+                        int64_t n_items, const float* user_add, const float* item_add, const int64_t* filt_off,
+                        const int32_t* filt_ids, const int64_t* gold_off, const int32_t* gold_ids, int64_t n_gold,
+                        int64_t block_golds, int nsplit, int32_t* ranks, void* ws, void* stream);
+int ktup_eval_cfkg_ranks_supported(int d, int64_t n_cand, int64_t block_golds);
+size_t ktup_eval_cfkg_ranks_workspace_bytes(int d, int64_t nq, int64_t n_cand, int64_t n_gold, int64_t block_golds);
+int ktup_eval_cfkg_ranks(const float* U, int64_t ldu, const float* R, int64_t ldr, int64_t rel, const float* E, int64_t lde,
+                         int64_t n_ent, const int64_t* cand_ids, int64_t n_cand, int d, const int64_t* u_ids, int64_t nq, int l1,
+                         const int64_t* filt_off, const int32_t* filt_ids, const int64_t* gold_off, const int32_t* gold_ids,
+                         int64_t n_gold, int64_t block_golds, int nsplit, int32_t* ranks, void* ws, void* stream);
+
 /* =================================================================== the TransR training step in one launch (csrc/ktup_transr_step.hip)
  * transR.py:65-78 + utils/misc.py:21-26 scored, and knowledge_representation.py:176-204's step built, for the KG driver and CKE.
  * h / t / r hold [pos ; neg], 2B entries each (the layout of ktup_train_kg_step and ktup_feed_kg): rows k and k + B are the positive

@@ -16,7 +16,8 @@
 //   * L1: on the VALU against the same stage, the wave's 16 query rows in LDS.
 // The spare slot also carries whether the candidate's entity row exists.
 #include "ktup_rows.h"
-#include "ktup_sweep_pass.h"
+#include "ktup_cfkg_norm.h"
+#include "ktup_sweep_scorers.h"
 
 using namespace ktup;
 
@@ -145,97 +146,7 @@ extern "C" int ktup_train_cfkg_rec_step(const float* U, int64_t ldu, const float
 namespace ktup {
 namespace {
 
-// |e|^2 of every candidate, once per pass (squared L2 only): 16 lanes per candidate; a candidate without an entity row gets 0.
-__global__ __launch_bounds__(256) void cfkg_cand_norm_kernel(const float* __restrict__ E, int64_t lde, int64_t n_ent,
-                                                             const int64_t* __restrict__ cand_ids, int64_t n_cand, int d,
-                                                             float* __restrict__ out) {
-  const int l = threadIdx.x & 15;
-  for (int64_t c = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); c < n_cand; c += (int64_t)gridDim.x * 16) {
-    const int64_t id = cand_ids ? cand_ids[c] : c;
-    float s = 0.f;
-    if (id >= 0 && id < n_ent) {
-      const float* row = E + id * lde;
-      for (int k = l; k < d; k += 16) s = fmaf(row[k], row[k], s);
-    }
-    s = group_sum<16>(s);
-    if (l == 0) out[c] = s;
-  }
-}
-
-struct CfkgPassArgs {
-  SweepArgs sw;
-  const float* U; int64_t ldu;
-  const float* R; int64_t ldr, rel;
-  const float* E; int64_t lde, n_ent;
-  const int64_t* cand_ids;              // NULL: candidate j is row j
-  const float* enorm;                   // [n_cand] |e|^2 (squared L2); NULL under L1
-};
-
-// What cfkg_pass_kernel adds to the sweep.  The sweep ranks s = -distance descending, like the inner-product pass: ascending
-// distance, ties -> lower j.
-template <int KS, bool L1, int STC = 0>
-struct CfkgScorer {
-  using G = SweepGeom<KS, STC>;
-  static constexpr int CROW4 = KS | 1;                                    // L1: float4 pitch of a query row in LDS
-  static constexpr size_t CW = L1 ? (size_t)16 * CROW4 * 16 : 0;          // L1: a wave's 16 query rows
-  static constexpr size_t LDS = 4 * CW;
-  const CfkgPassArgs& a;
-  float cn[4] = {0.f, 0.f, 0.f, 0.f};                                     // squared L2: |c|^2 of the users of this lane's accumulator rows
-  const v4* cw = nullptr;                                                 // L1: the query rows of those four users, [4][CROW4]
-  KTUP_DEV float query(int64_t u, int k) const { return a.U[u * a.ldu + k] + a.R[a.rel * a.ldr + k]; }
-  KTUP_DEV void hold(const float (&av)[KS], char* smem, int64_t, const bool (&)[4], int kq, int j) {
-    if constexpr (L1) {
-      float* cwf = reinterpret_cast<float*>(smem + (size_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * CW);   // [16][CROW4] float4
-#pragma unroll
-      for (int s = 0; s < KS; ++s) cwf[(j * CROW4 + s) * 4 + kq] = av[s];
-      cw = reinterpret_cast<const v4*>(cwf) + 4 * kq * CROW4;
-    } else {
-      float cnj = 0.f;
-#pragma unroll
-      for (int s = 0; s < KS; ++s) cnj = fmaf(av[s], av[s], cnj);
-      cnj += __shfl_xor(cnj, 16, 64);
-      cnj += __shfl_xor(cnj, 32, 64);                                     // |c|^2 of user j on every lane (., j)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) cn[reg] = __shfl(cnj, 4 * kq + reg, 64);
-    }
-  }
-  // a cand_ids entry outside [0, n_ent) is never ranked and never dereferenced: the stage reads row 0 in its place
-  KTUP_DEV const float* row(int64_t c, bool& live) const {
-    const int64_t id = a.cand_ids ? a.cand_ids[c] : c;
-    live = id >= 0 && id < a.n_ent;
-    return a.E + (live ? id : (int64_t)0) * a.lde;
-  }
-  KTUP_DEV v4 spare(int64_t c, bool live) const { return (v4){a.enorm ? a.enorm[c] : 0.f, live ? 1.f : 0.f, 0.f, 0.f}; }
-  // acc: c.e on the matrix cores (squared L2), or the distance itself on the VALU against the same stage (L1): every lane owns the
-  // 4 users x 16-candidate-tile slots the MFMA would have given it
-  KTUP_DEV void tile_math(const float (&av)[KS], const v4* eb, int kq, v4 (&acc)[G::NSUB]) const {
-    if constexpr (L1) {
-#pragma unroll 2
-      for (int s = 0; s < KS; ++s) {
-        v4 cq[4];
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) cq[reg] = cw[reg * CROW4 + s];
-#pragma unroll
-        for (int t = 0; t < G::NSUB; ++t) {
-          const v4 e = eb[t * 16 * G::ROW4 + s];
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg) {
-            const v4 z = cq[reg] - e;
-            acc[t][reg] += (fabsf(z[0]) + fabsf(z[1])) + (fabsf(z[2]) + fabsf(z[3]));
-          }
-        }
-      }
-    } else {
-      sweep_tile_dot<KS>(av, eb, kq, acc);
-    }
-  }
-  KTUP_DEV v4 staged(const v4* slot) const { return *slot; }
-  KTUP_DEV bool live(const v4& spare) const { return spare[1] != 0.f; }
-  KTUP_DEV float score(float acc, int reg, const v4& spare) const {
-    return -(L1 ? acc : __fadd_rn(fmaf(-2.f, acc, cn[reg]), spare[0]));    // |c|^2 - 2 c.e + |e|^2
-  }
-};
-
+// (the scorer, CfkgScorer, is in ktup_sweep_scorers.h and the |e|^2 launch in ktup_cfkg_norm.h: the gold-rank pass runs them too)
 template <int KS, bool VEC, bool L1>
 __global__ __launch_bounds__(256, 2) void cfkg_pass_kernel(CfkgPassArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];

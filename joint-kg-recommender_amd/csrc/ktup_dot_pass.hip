@@ -5,46 +5,15 @@
 // Reference: bprmf.py:51-54 / fm.py:69-80 / CKE.py:142-153 / cofm.py:127-141 produce a (B x N) matrix per batch of 512 users,
 // which utils/misc.py:186-248 copies to the host, argsorts and walks.  The per-batch route of this build keeps that shape on the
 // device (ktup_eval_bprmf_scores, two torch adds, ktup_eval_topk_filtered, ktup_eval_rec_metrics per batch).  Here the sweep is
-// ktup_sweep_pass.h's; dot_pass_kernel supplies the scorer: the query row is U[u], candidate j is item row j, the item's additive
+// ktup_sweep_pass.h's; dot_pass_kernel supplies the scorer (DotScorer, ktup_sweep_scorers.h: the gold-rank pass runs it too): the query row is U[u], candidate j is item row j, the item's additive
 // term rides in the row's spare slot, and a score is the MFMA dot product -- bit for bit the fmaf chain of K11 (bprmf_eval_kernel)
 // -- then the two separately rounded adds, so the scores and with them the ranked lists are the per-batch route's bits.
 // ktup_eval_dot_topk keeps a user's list as one key per lane (topn <= 16); ktup_eval_dot_topk_wide is the same pass on lists of two
 // or four 16-key segments (dot_pass_wide_kernel: topn <= 32, <= 64).
-#include "ktup_sweep_pass.h"
+#include "ktup_sweep_scorers.h"
 
 namespace ktup {
 namespace {
-
-struct DotArgs {
-  const float* U; int64_t ldu;
-  const float* I; int64_t ldi;
-  const float *user_add, *item_add;     // NULL = none
-  SweepArgs sw;
-};
-
-template <int KS>
-struct DotScorer {
-  static constexpr size_t LDS = 0;
-  const DotArgs& a;
-  float uadd[4] = {0.f, 0.f, 0.f, 0.f};
-  KTUP_DEV float query(int64_t u, int k) const { return a.U[u * a.ldu + k]; }
-  KTUP_DEV void hold(const float (&)[KS], char*, int64_t u0, const bool (&in)[4], int kq, int) {
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg)
-      if (a.user_add && in[reg]) uadd[reg] = a.user_add[u0 + 4 * kq + reg];
-  }
-  KTUP_DEV const float* row(int64_t c, bool& live) const { live = true; return a.I + c * a.ldi; }
-  KTUP_DEV v4 spare(int64_t c, bool) const { return (v4){a.item_add ? a.item_add[c] : 0.f, 0.f, 0.f, 0.f}; }
-  KTUP_DEV void tile_math(const float (&av)[KS], const v4* eb, int kq, v4 (&acc)[SweepGeom<KS>::NSUB]) const { sweep_tile_dot<KS>(av, eb, kq, acc); }
-  KTUP_DEV float staged(const v4* slot) const { return *reinterpret_cast<const float*>(slot); }
-  KTUP_DEV bool live(float) const { return true; }
-  KTUP_DEV float score(float dot, int reg, float iadd) const {
-    float s = dot;
-    if (a.user_add) s = __fadd_rn(s, uadd[reg]);
-    if (a.item_add) s = __fadd_rn(s, iadd);
-    return s;
-  }
-};
 
 template <int KS, bool VEC>
 __global__ __launch_bounds__(256, 2) void dot_pass_kernel(DotArgs a) {

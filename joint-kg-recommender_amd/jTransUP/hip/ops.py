@@ -1181,6 +1181,99 @@ def _eval_cfkg_topk(entry, topn_max, U, R, rel, E, u, topn, l1, cand_ids, filt_o
                        with_scores)
 
 
+_BLOCK_GOLDS = {}
+
+
+def _block_golds(gold_off):
+    """Largest number of gold entries of a 64-user block of a pass's CSR index (block_golds of ktup_eval_dot_ranks): one device read
+    per index, like _max_golds."""
+    key = (gold_off.data_ptr(), gold_off.numel())
+    hit = _BLOCK_GOLDS.get(key)
+    if hit is None or hit[0] is not gold_off:
+        if len(_BLOCK_GOLDS) > 64:
+            _BLOCK_GOLDS.clear()
+        nq = gold_off.numel() - 1
+        if nq < 1:
+            most = 0
+        else:
+            cuts = gold_off[torch.arange(0, nq + 64, 64, device=gold_off.device).clamp_(max=nq)]
+            most = int((cuts[1:] - cuts[:-1]).max().item())
+        hit = _BLOCK_GOLDS[key] = (gold_off, most)
+    return hit[1]
+
+
+def _rank_sweep(entry, who, head, tail, d, nq, n, gold_off, gold_ids, filt_off, filt_ids, nsplit, dev):
+    """The tail of the one-sweep gold-rank wrappers: entry(*head, u, nq, *tail, filters, golds, n_gold, block_golds, nsplit, ranks,
+    workspace, stream) -> int32 [n_gold]; None where the entry point declines the shape."""
+    filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
+    _csr_offsets(who, nq, gold_off, filt_off)
+    if gold_ids.dtype != torch.int32 or gold_off.dtype != torch.int64 or gold_ids.device != dev or gold_off.device != dev:
+        raise L.KtupError('%s: gold_off must be an int64 and gold_ids an int32 tensor on %s' % (who, dev))
+    n_gold = gold_ids.numel()
+    ranks = torch.empty(n_gold, dtype=torch.int32, device=dev)
+    if nq == 0 or n_gold == 0:
+        return ranks
+    if n == 0 or not (0 < d <= 256):
+        return None
+    lib = L.load()
+    bg = _block_golds(gold_off)
+    if not getattr(lib, entry + '_supported')(d, n, bg):
+        return None
+    ws = _scratch(getattr(lib, entry + '_workspace_bytes')(d, nq, n, n_gold, bg), dev)
+    try:
+        L.call(entry, *head, nq, *tail, _p(filt_off), _p(filt_ids), _p(gold_off), _p(gold_ids), n_gold, bg, int(nsplit), _p(ranks), _p(ws),
+               _stream(dev))
+    except L.KtupError as e:
+        if e.code == L.ERR_UNSUPPORTED:
+            return None
+        raise
+    return ranks
+
+
+@torch.no_grad()
+def eval_dot_ranks(U, I, u, gold_off, gold_ids, filt_off=None, filt_ids=None, user_add=None, item_add=None, nsplit=0):
+    """The filtered rank of every gold item of a whole evaluation pass of the inner-product recommenders in one sweep
+    (ktup_eval_dot_ranks): gold_ranks(descending=True) on the scores of eval_dot_topk -- the same bits, no (users x items) matrix.
+    gold_off: int64 (len(u) + 1,) absolute offsets into gold_ids (int32), per user of `u`.  -> int32 [len(gold_ids)], -1 for a gold
+    that is filtered or outside the catalogue; None where the entry point declines (d > 256, a 64-user block with more gold entries
+    than its LDS holds): keep the matrix route.  One device read per CSR index (the largest block), none after: the call can be
+    captured in a graph."""
+    dev = _dev(_table('user table', U)); _table('item table', I)
+    if I.device != dev or I.shape[1] != U.shape[1]:
+        raise L.KtupError('user and item tables must share the device and the embedding size')
+    u = _ids('u_ids', u, dev)
+    nq, d, ni = u.numel(), U.shape[1], I.shape[0]
+
+    def _term(name, t, n):
+        if t is None:
+            return None
+        if t.device != dev or t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n:
+            raise L.KtupError('%s must be a 1-D fp32 tensor of %d entries on %s' % (name, n, dev))
+        return t.detach().contiguous()
+    user_add, item_add = _term('user_add', user_add, nq), _term('item_add', item_add, ni)
+    return _rank_sweep('ktup_eval_dot_ranks', 'eval_dot_ranks', (_p(U), U.stride(0), _p(I), I.stride(0), d, _p(u)), (ni, _p(user_add), _p(item_add)),
+                       d, nq, ni, gold_off, gold_ids, filt_off, filt_ids, nsplit, dev)
+
+
+@torch.no_grad()
+def eval_cfkg_ranks(U, R, rel, E, u, l1, gold_off, gold_ids, cand_ids=None, filt_off=None, filt_ids=None, nsplit=0):
+    """eval_dot_ranks for CFKG (ktup_eval_cfkg_ranks): gold_ranks(descending=False) on the distances of eval_cfkg_topk, the same bits.
+    Gold and filter ids are in candidate (j) space; a gold whose candidate has no entity row gets -1."""
+    dev = _dev(_table('user table', U)); _table('relation table', R); _table('entity table', E)
+    if R.device != dev or E.device != dev or R.shape[1] != U.shape[1] or E.shape[1] != U.shape[1]:
+        raise L.KtupError('user, relation and entity tables must share the device and the embedding size')
+    if not (0 <= int(rel) < R.shape[0]):
+        raise L.KtupError('relation row %d outside the %d rows of the relation table' % (int(rel), R.shape[0]))
+    u = _ids('u_ids', u, dev)
+    if cand_ids is not None:
+        cand_ids = _ids('cand_ids', cand_ids, dev)
+    nq, d, ne = u.numel(), U.shape[1], E.shape[0]
+    nc = ne if cand_ids is None else cand_ids.numel()
+    head = (_p(U), U.stride(0), _p(R), R.stride(0), int(rel), _p(E), E.stride(0), ne, _p(cand_ids), nc, d, _p(u))
+    return _rank_sweep('ktup_eval_cfkg_ranks', 'eval_cfkg_ranks', head, (int(bool(l1)),), d, nq, nc, gold_off, gold_ids, filt_off, filt_ids, nsplit,
+                       dev)
+
+
 TOPN_MAX, TOPN_WIDE_MAX = 16, 64       # csrc/ktup_topn.h: one key per lane of a 16-lane row; up to four such segments
 # Is the wide-list sweep the route of a model's evaluate_topk at 17 <= topn <= 64 when nobody says otherwise (library option
 # eval_wide_topn / KTUP_EVAL_WIDE_TOPN = -1; 0: never, the batch walk stays; 1: always)?  profiles/wide_topn_times.txt: the sweep

@@ -71,6 +71,14 @@ class CFKG(nn.Module, GradToggle):
         return sweep and sweep(self.user_embeddings.weight, self.rel_embeddings.weight, self.rel_total - 1, self.item_embeddings.weight,
                                u_ids, topn, self.L1_flag, cand_ids=items, filt_off=filt_off, filt_ids=filt_ids)
 
+    def rank_items(self, u_ids, items, gold_off, gold_ids, filt_off=None, filt_ids=None):
+        """The filtered rank of every gold item of every user of `u_ids` in one sweep (ops.eval_cfkg_ranks): gold_ranks(ascending) on
+        evaluate_topk's distances -- the same bits -- against the entity rows `items` (int64 ids; None = every row), no (users x
+        candidates) matrix.  Gold and filter ids are positions in `items`.  -> int32 [len(gold_ids)], -1 for a gold that is itself
+        filtered or has no row; None where the sweep declines (the caller keeps the matrix route)."""
+        return ops.eval_cfkg_ranks(self.user_embeddings.weight, self.rel_embeddings.weight, self.rel_total - 1, self.item_embeddings.weight,
+                                   u_ids, self.L1_flag, gold_off, gold_ids, cand_ids=items, filt_off=filt_off, filt_ids=filt_ids)
+
     def _cand(self, all_e_ids):
         return self.ent_embeddings(all_e_ids).detach().contiguous() if all_e_ids is not None else None
 

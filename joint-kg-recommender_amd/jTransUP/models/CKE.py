@@ -85,6 +85,13 @@ class CKE(nn.Module, GradToggle):
         with torch.no_grad():
             return sweep(self.user_embeddings.weight, self._item_side().contiguous(), u_ids, topn, filt_off, filt_ids)
 
+    def rank_items(self, u_ids, items, gold_off, gold_ids, filt_off=None, filt_ids=None):
+        """The filtered rank of every gold item of every user of `u_ids` in one sweep (ops.eval_dot_ranks) on evaluate_topk's item side
+        and score bits, no (users x items) matrix.  `items` is unused.  -> int32 [len(gold_ids)], -1 for a gold that is itself
+        filtered; None where the sweep declines (the caller keeps the matrix route)."""
+        with torch.no_grad():
+            return ops.eval_dot_ranks(self.user_embeddings.weight, self._item_side().contiguous(), u_ids, gold_off, gold_ids, filt_off, filt_ids)
+
     def prepare_entities(self):
         """Entity side of evaluateHead / evaluateTail, once per evaluation pass (`ents=`)."""
         return ops.eval_transr_entities(self.ent_embeddings.weight, self.proj_embeddings.weight, self.rel_embeddings.weight.shape[0], self.L1_flag)

@@ -393,6 +393,43 @@ def summarize_rec(FLAGS, results, logger):
     return f1, p, r, hit, ndcg
 
 
+def rec_rank_pass(FLAGS, score_fn, eval_iter, eval_dict, all_dicts, descending, n_cand, logger, rank_fn=None, pass_descending=False,
+                  sharded=False, shard_fn=None):
+    """KTUP_REC_RANKS=1: after a periodic rec evaluation, where every held-out item stands -- MRR, mean rank and AUC
+    (utils/ranking.py rec_rank_metrics) from the filtered rank of every gold item of the same users and index, logged on a line of
+    its own after summarize_rec's (these are not metrics of the reference: its log lines and return values stay as they are).
+    Route `sweep`: rank_fn(users, g_off, g_ids, f_off, f_ids) (a model's rank_items: one sweep, no score matrix) where it ranks in
+    the order asked for and answers; `walk` otherwise (and under KTUP_EVAL_PASS=0): score_fn per batch + ops.gold_ranks.  Unset or 0: nothing is computed or
+    logged.  Sharded candidates and runs with more than one process skip the pass with one line saying so.  -> the three or None."""
+    if os.environ.get('KTUP_REC_RANKS', '0') in ('', '0'):
+        return None
+    if sharded or (shard_fn is not None and _shard_mode(FLAGS, shard_fn(), False)) or not _single_process():
+        logger.info('rec rank pass skipped: KTUP_REC_RANKS covers neither sharded candidates nor runs with more than one process.')
+        return None
+    from jTransUP.hip import ops
+    from jTransUP.utils.ranking import rec_rank_metrics
+    index = rank_index(eval_iter, eval_dict, all_dicts)
+    n_gold = len(index.g_ids_h)
+    if n_gold == 0:
+        return None
+    ranks, route = None, 'sweep'
+    if rank_fn is not None and bool(descending) == bool(pass_descending) and os.environ.get('KTUP_EVAL_PASS', '1') != '0':
+        fo, fi = (index.f_off, index.f_ids) if index.has_filter else (None, None)
+        ranks = rank_fn(ids([u for batch in eval_iter for u in batch]), index.g_off, index.g_ids[:n_gold], fo, fi)
+    if ranks is None:
+        route, parts = 'walk', []
+        for u_ids in eval_iter:
+            s, e = index.rows_of(u_ids)
+            f_off, f_ids = index.filter_slice(s, e)
+            g_off, g_ids, g_off_h, _ = index.gold_slice(s, e)
+            if int(g_off_h[-1]) > 0:
+                parts.append(ops.gold_ranks(score_fn(batch_ids(u_ids)), descending, g_off, g_ids, f_off, f_ids)[:int(g_off_h[-1])])
+        ranks = torch.cat(parts)
+    mrr, mean_rank, auc = rec_rank_metrics(ranks[:n_gold].cpu().numpy(), index.g_off_h, index.n_neg(n_cand))
+    logger.info('mrr:{:.4f}, mean rank:{:.4f}, auc:{:.4f} ({}).'.format(mrr, mean_rank, auc, route))
+    return mrr, mean_rank, auc
+
+
 def summarize_kg(FLAGS, head_results, tail_results, logger):
     as_cols = lambda res: res if isinstance(res, np.ndarray) else np.array([row[:2] for row in res])
     head_hit, head_rank = as_cols(head_results).mean(axis=0)

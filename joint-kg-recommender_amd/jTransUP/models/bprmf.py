@@ -39,3 +39,9 @@ class BPRMF(nn.Module, GradToggle):
         wide lists serve it, ops.topk_sweep_for)."""
         sweep = ops.topk_sweep_for(topn, ops.eval_dot_topk, ops.eval_dot_topk_wide, 'dot')
         return sweep and sweep(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, topn, filt_off, filt_ids)
+
+    def rank_items(self, u_ids, items, gold_off, gold_ids, filt_off=None, filt_ids=None):
+        """The filtered rank of every gold item of every user of `u_ids` in one sweep (ops.eval_dot_ranks): gold_ranks on `evaluate`'s
+        scores without the (users x items) matrix, on evaluate_topk's score bits.  `items` is unused.  -> int32 [len(gold_ids)], -1 for
+        a gold that is itself filtered; None where the sweep declines (the caller keeps the matrix route)."""
+        return ops.eval_dot_ranks(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, gold_off, gold_ids, filt_off, filt_ids)

@@ -72,6 +72,17 @@ class coFM(nn.Module, GradToggle):
             return sweep(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, topn, filt_off, filt_ids,
                          user_add=user_add, item_add=self.item_bias.weight)
 
+    def rank_items(self, u_ids, items, gold_off, gold_ids, filt_off=None, filt_ids=None):
+        """The filtered rank of every gold item of every user of `u_ids` in one sweep (ops.eval_dot_ranks), with the tables and the
+        bias terms evaluate_topk passes: gold_ranks on its score bits, no (users x items) matrix.  `items` is unused.  -> int32
+        [len(gold_ids)], -1 for a gold that is itself filtered; None where the sweep declines (the caller keeps the matrix route)."""
+        if self.is_share:                  # (the candidates are rows of the entity table: the matrix route, as evaluate_topk)
+            return None
+        with torch.no_grad():
+            user_add = self.bias + self.user_bias(u_ids)
+            return ops.eval_dot_ranks(self.user_embeddings.weight, self.item_embeddings.weight, u_ids, gold_off, gold_ids, filt_off, filt_ids,
+                                      user_add=user_add, item_add=self.item_bias.weight)
+
     def _cand(self, all_e_ids):
         return self.ent_embeddings(all_e_ids).detach().contiguous() if (all_e_ids is not None and self.is_share) else None
 

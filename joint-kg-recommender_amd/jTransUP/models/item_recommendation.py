@@ -36,12 +36,18 @@ def evaluate(FLAGS, model, eval_iter, eval_dict, all_dicts, logger, eval_descend
     if native is not None and not is_report:
         results = D.rec_eval_pass(FLAGS, None, eval_iter, eval_dict, all_dicts, eval_descending, want_rows=False, shard=native.rec_shard())
         perf = D.summarize_rec(FLAGS, results, logger)
+        D.rec_rank_pass(FLAGS, None, eval_iter, eval_dict, all_dicts, eval_descending, model.item_total, logger, sharded=True)
         model.enable_grad()
         return perf
     results = D.rec_eval_pass(FLAGS, score_fn, eval_iter, eval_dict, all_dicts, eval_descending, want_rows=is_report,
                               shard=rec_shard_fn(model), pass_fn=pass_fn, graph_key=D.model_graph_key(model) if pass_fn else None,
                               pass_descending=getattr(model, 'topk_descending', False))
     perf = D.summarize_rec(FLAGS, results, logger)
+    # KTUP_REC_RANKS=1: MRR, mean rank and AUC of the same users on a line of their own (model.rank_items' sweep, or the batch walk)
+    rank_fn = (lambda u, go, gi, fo, fi: model.rank_items(u, None, go, gi, fo, fi)) if hasattr(model, 'rank_items') else None
+    D.rec_rank_pass(FLAGS, score_fn, eval_iter, eval_dict, all_dicts, eval_descending, model.item_total, logger, rank_fn=rank_fn,
+                    pass_descending=getattr(model, 'topk_descending', False),
+                    shard_fn=lambda: rec_shard_fn(model))
     if is_report:
         D.report_rec(FLAGS, model, results, all_dicts, eval_dict, logger, FLAGS.model_type in ('transup', 'jtransup', 'cjtransup'))
     model.enable_grad()

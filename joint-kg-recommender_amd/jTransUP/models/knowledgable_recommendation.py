@@ -85,6 +85,16 @@ def evaluateRec(FLAGS, model, eval_iter, eval_dict, all_dicts, i_map, logger, ev
                                   shard=rec_shard_fn(model), pass_fn=pass_fn, graph_key=graph_key,
                                   pass_descending=getattr(model, 'topk_descending', False))
     perf = D.summarize_rec(FLAGS, results, logger)
+    # KTUP_REC_RANKS=1: MRR, mean rank and AUC of the same users on a line of their own.  model.rank_items' sweep where evaluate_topk's
+    # would serve (own item table, or CFKG's entity-row candidates), the batch walk otherwise (TUP / KTUP, -share_embeddings)
+    rank_fn = None
+    if hasattr(model, 'rank_items') and not FLAGS.share_embeddings:
+        rank_fn = lambda u, go, gi, fo, fi: model.rank_items(u, None, go, gi, fo, fi)
+    elif hasattr(model, 'rank_items') and getattr(model, 'topk_takes_candidates', False):
+        rank_fn = lambda u, go, gi, fo, fi: model.rank_items(u, _pass_candidates(model, i_map), go, gi, fo, fi)
+    D.rec_rank_pass(FLAGS, score_fn, eval_iter, eval_dict, all_dicts, eval_descending, len(i_map), logger, rank_fn=rank_fn,
+                    pass_descending=getattr(model, 'topk_descending', False),
+                    sharded=native is not None and not is_report, shard_fn=lambda: rec_shard_fn(model))
     if is_report:
         D.report_rec(FLAGS, model, results, all_dicts, eval_dict, logger, FLAGS.model_type in ('transup', 'jtransup'))
     model.enable_grad()

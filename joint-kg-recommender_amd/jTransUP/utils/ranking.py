@@ -51,6 +51,7 @@ class RankIndex(object):
         self.f_off_h = np.asarray(f_off, dtype=np.int64)
         self.g_off_h = np.asarray(g_off, dtype=np.int64)
         self.g_ids_h = np.asarray(g_ids, dtype=np.int32)
+        self.f_ids_h = np.asarray(f_ids, dtype=np.int32)
         self.f_off = torch.from_numpy(self.f_off_h).to(device)
         self.g_off = torch.from_numpy(self.g_off_h).to(device)
         self.f_ids = torch.from_numpy(np.asarray(f_ids if f_ids else [0], dtype=np.int32)).to(device)
@@ -87,6 +88,18 @@ class RankIndex(object):
             hit = self._fslice[(s, e)] = (self.f_off[s:e + 1] - lo, self.f_ids[lo:])
         return hit
 
+    def n_neg(self, n_cand):
+        """Per key: how many of the candidates 0 .. n_cand - 1 are neither in its filter set nor among its golds (rec_rank_metrics)."""
+        hit = self._memo.get(('n_neg', n_cand))
+        if hit is None:
+            hit = np.empty(len(self.keys), dtype=np.int64)
+            for b in range(len(self.keys)):
+                out = set(self.f_ids_h[self.f_off_h[b]:self.f_off_h[b + 1]].tolist()) if self.has_filter else set()
+                out.update(self.g_ids_h[self.g_off_h[b]:self.g_off_h[b + 1]].tolist())
+                hit[b] = n_cand - sum(1 for i in out if 0 <= i < n_cand)
+            self._memo[('n_neg', n_cand)] = hit
+        return hit
+
     def gold_slice(self, s, e):
         hit = self._gslice.get((s, e))
         if hit is None:
@@ -109,6 +122,37 @@ def rec_metrics(top_ids, gold):
         f1 = 2 * p * r / (p + r)
         ndcg = ndcg_at_k(hits, k)
     return f1, p, r, hit, ndcg
+
+
+def rec_rank_metrics(ranks, gold_off, n_neg):
+    """(mrr, mean_rank, auc) in float64 from the filtered 0-based rank of every gold entry (ops.gold_ranks / ops.eval_dot_ranks:
+    candidates ordered before the gold that are neither filtered nor gold), the CSR offsets of the users' gold lists and n_neg[u] =
+    the number of u's ranked candidates that are neither filtered nor gold.  Entries with rank -1 are dropped.
+        mean rank  the mean of the ranks over all entries
+        MRR        the mean over users with a ranked gold of 1 / (1 + min rank): the best gold has no gold before it, so its rank
+                   is its place in the train-filtered list
+        AUC        the mean over users with a ranked gold and n_neg > 0 of 1 - mean(rank) / n_neg: the share of (gold, other) pairs
+                   the model orders correctly (what BPR optimises)
+    A quantity with nothing to average is 0."""
+    ranks = np.asarray(ranks, dtype=np.int64)
+    gold_off = np.asarray(gold_off, dtype=np.int64)
+    n_neg = np.asarray(n_neg, dtype=np.float64)
+    nq = len(gold_off) - 1
+    users = np.repeat(np.arange(nq, dtype=np.int64), np.diff(gold_off))
+    ranks = ranks[:len(users)]
+    ok = ranks >= 0
+    r, us = ranks[ok].astype(np.float64), users[ok]
+    if r.size == 0:
+        return 0.0, 0.0, 0.0
+    cnt = np.bincount(us, minlength=nq)
+    has = cnt > 0
+    best = np.full(nq, np.inf)
+    np.minimum.at(best, us, r)
+    mrr = float((1.0 / (1.0 + best[has])).mean())
+    sums = np.bincount(us, weights=r, minlength=nq)
+    pairs = has & (n_neg > 0)
+    auc = float((1.0 - sums[pairs] / cnt[pairs] / n_neg[pairs]).mean()) if pairs.any() else 0.0
+    return mrr, float(r.mean()), auc
 
 
 def _as_device_rows(pred_scores, device):
