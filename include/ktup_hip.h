@@ -1146,6 +1146,36 @@ int ktup_eval_cfkg_ranks(const float* U, int64_t ldu, const float* R, int64_t ld
                          const int64_t* filt_off, const int32_t* filt_ids, const int64_t* gold_off, const int32_t* gold_ids,
                          int64_t n_gold, int64_t block_golds, int nsplit, int32_t* ranks, void* ws, void* stream);
 
+/* =================================================================== gold ranks of a TUP / KTUP evaluation pass (csrc/ktup_pref_rank_pass.hip)
+ * The rank form of the preference-space list pass: ktup_eval_gold_ranks(descending = 0) applied to the scores of ktup_eval_pref_topk,
+ * without the (users x items) matrix.  The table / pref_ws / u_ids arguments are ktup_eval_pref_topk's (E == NULL with item2ent ==
+ * NULL: TUP), the filter / gold / n_gold / block_golds / nsplit / ranks / ws / stream arguments and their rules ktup_eval_dot_ranks':
+ *     ranks[e] = #{items of the user ordered before gold entry e that are neither in the user's filter list nor among its golds}
+ * in the list pass's key order -- ascending score, ties -> lower item id -- on the list pass's own score BITS (one copy of the score
+ * code, csrc/ktup_pref_q_tile.h, and of the operand tables, built by the list pass's own host function), so a gold that
+ * ktup_eval_pref_topk(_wide) shows at place p has rank p - (golds listed before it).  ranks[e] = -1: the gold id is in the user's own
+ * filter list or outside [0, n_items).  A rank is a sum of integer counts: the same integer at every nsplit and every order of u_ids
+ * (duplicates allowed); no float atomics.  (A block that holds more gold entries than the caller announced is not ranked: all -1.)
+ *
+ * Served: the soft gate with squared L2 (l1 == 0) at d in {64, 100, 128}, 1 <= n_pref <= 32, n_items < 2^31, library option eval_mc
+ * != 0, pitched or unaligned U / I / E as far as the list pass takes them, at most KTUP_PREF_RANK_BLOCK_GOLDS gold entries per
+ * 64-user block.  The cap is LDS arithmetic: two 16-item tiles + four waves' user scalars (1,024 B) + the block's offsets (320 B) +
+ * 12 bytes per gold entry must fit twice per CU (81,920 B each); the largest tiles, d = 128 with more than 20 preferences, are
+ * 2 x 14,656 B, which leaves room for 4,272 entries: 3,072 fit at every covered geometry (an ml1m-size test split has about 1,100).
+ * KTUP_ERR_UNSUPPORTED before any launch (and _supported 0, workspace size 0): l1 != 0, any other d (256 included), n_pref > 32,
+ * eval_mc == 0, n_items >= 2^31, block_golds above the cap -- the caller keeps the matrix route; the entry point never truncates.
+ * nq == 0 or n_gold == 0 is KTUP_OK and launches nothing.  Null or short arguments are KTUP_ERR_INVALID_ARG before any launch.
+ * nsplit: 0 = chosen by the library, else forced (at most 32).  `ws`: _workspace_bytes for the same arguments, 16-byte aligned.  No
+ * host synchronisation: the call can be captured into a graph.                                                                    */
+#define KTUP_PREF_RANK_BLOCK_GOLDS KTUP_RANK_BLOCK_GOLDS
+int ktup_eval_pref_ranks_supported(int d, int n_pref, int l1, int64_t n_items, int64_t block_golds);
+size_t ktup_eval_pref_ranks_workspace_bytes(int d, int n_pref, int l1, int64_t nq, int64_t n_items, int64_t n_gold, int64_t block_golds);
+int ktup_eval_pref_ranks(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* E, int64_t lde,
+                         const int32_t* item2ent, const float* pref_ws, int n_pref, int d, const int64_t* u_ids, int64_t nq,
+                         int64_t n_items, int l1, const int64_t* filt_off, const int32_t* filt_ids, const int64_t* gold_off,
+                         const int32_t* gold_ids, int64_t n_gold, int64_t block_golds, int nsplit, int32_t* ranks, void* ws,
+                         void* stream);
+
 /* =================================================================== the TransR training step in one launch (csrc/ktup_transr_step.hip)
  * transR.py:65-78 + utils/misc.py:21-26 scored, and knowledge_representation.py:176-204's step built, for the KG driver and CKE.
  * h / t / r hold [pos ; neg], 2B entries each (the layout of ktup_train_kg_step and ktup_feed_kg): rows k and k + B are the positive

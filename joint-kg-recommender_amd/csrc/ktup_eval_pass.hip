@@ -38,16 +38,17 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "ktup_common.h"
 #include "ktup_lane_swap.h"
 #include "ktup_pref_geom.h"
+#include "ktup_pref_q_tile.h"
 #include "ktup_topn.h"
 
 namespace ktup {
 namespace {
 
-constexpr int IBT = 16;        // items per LDS tile
 // LDS per wave of the sweep: user scalars [16][4] | filter bits [16][bm_words] | pending candidates [16][PCAP] u64 | lists [16][SEG][16]
 // u64 | n-th keys [16] u64.  SEG: 16-key segments of a user's list (ktup_topn.h: 1 = the narrow list, 2 or 4 = the wide ones).  The
 // kernel finds the last three from the END of its wave's share: WAVE_TAIL<SEG> is the one place that says how long that end is, for the
@@ -110,51 +111,8 @@ KTUP_DEV void filter_bitmap_wave(const FiltBm& f, int64_t u0, uint32_t* lbm, int
 }
 
 // ================================================================================================ preference-space formulation
-// Six d-long products per pair (u.NV, NU.v, AU.C0, AU.NV, NU.C0, NU.NV: round 2's first fused pass, 0.39 ms per ml1m sweep) are
-// more work than the model needs.  With the soft gate every vector of the score lives in
-//   span{x} + span{Ar_p} + span{Cn_p}   (x = u or v;  RU = sum_p L_p Ar_p,  NU = sum_p L_p Cn_p,  L = Alog x, P <= 32 preferences)
-// so every user x item cross term except u.v is a P-long contraction of per-row P-vectors (L, Rx = Ar x, Nx = Cn x) through the
-// three P x P Gram matrices G_RR = Ar Ar^T, G_RN = Ar Cn^T, G_NN = Cn Cn^T:
-//   s  cross = u.NV - v.NU            = [ Nu ; -L ]                          . [ LV ; Nv ]          K = 2 P
-//   an cross = AU.NV - C0.NU          = [ Nu + G_RN^T L + G_RN L ; -L ]      . [ LV ; Nv ]          K = 2 P   (same B)
-//   nn cross = 2 NU.NV                = [ 2 G_NN L ]                         . [ LV ]               K = P     (same B)
-//   aa cross = -2 AU.C0               = [ -2u ; -2L ; 2 (Ru + G_RR L) ]      . [ v ; Rv ; LV ]      K = d + 2 P
-// with the Gram products folded into the USER operand once per pass.  At d = 100, P = 20: 68 MFMAs (K padded to 16-blocks) and
-// 12 ds_read_b128 per 16 x 16 tile instead of 156 and 75; an item row is 160 floats instead of 300.  Scores agree with the
-// d-space kernels to fp32 rounding (a different association of the same sums), not bit for bit.
-template <int NCH_, int NP_>
-struct QGeom {
-  static constexpr int NCH = NCH_, D = 4 * NCH, NP = NP_, P4 = 4 * NP;
-  static constexpr int ROWB = D + 3 * P4;                       // item row: [x ; Rx ; L ; Nx]
-  static constexpr int RB4 = ROWB / 4;
-  // An item row is [x ; Rx ; L ; Nx | its 4 scalars (| one zero float4)] at an ODD float4 pitch (16 rows x 4 k-quads tile the LDS banks)
-  // -- in memory exactly as in LDS, so a tile of 16 consecutive items is ONE contiguous run of IBT * ROW4 float4 and travels by
-  // LDS-DMA (global_load_lds_dwordx4: destination = a wave-uniform LDS address + 16 B x lane): no staging registers (they were 12 of
-  // the lane's 168, with 9 more for the lane-constant source / destination addresses: 18 spilled), no ds_write pass (whose 16-lane
-  // groups straddled the row pads: ~16 two-way bank conflicts per tile)
-  static constexpr int ROW4 = (RB4 + 1) | 1;
-  static constexpr int GROW = 4 * ROW4;                         // floats per item row
-  static constexpr int TSLOTS = IBT * ROW4;                     // float4 per tile
-  static constexpr int DPW = ((TSLOTS + 63) / 64 + 3) / 4;      // DMA instructions per wave and tile (wave w issues pieces w, w + 4, ...)
-  static constexpr int SOFF4 = (D + P4) / 4;                    // float4 offset of [L ; Nx] inside a row
-  static constexpr int KA = (D + 2 * P4 + 15) / 16, KS = (2 * P4 + 15) / 16, KN = (P4 + 15) / 16;   // 16-blocks of K
-  static constexpr int NA = KA + 2 * KS + KN;                   // float4 per lane and 16-block of a user row in memory: [AA | S | AN | NN]
-  static constexpr int AROW = 16 * NA;                          // floats per user row
-  // What the sweep multiplies is the REAL K of each product: whole 16-blocks (one ds_read_b128 and four MFMAs each, k = 16 g + 4 kq + c)
-  // and then the remaining k-quads one MFMA each (one ds_read_b32, k = 16 F + 4 m + kq) -- the zero padding of the last 16-blocks
-  // was 8 of 68 MFMAs per tile at d = 100, P = 20
-  static constexpr int FA = (D + 2 * P4) / 16, TA = ((D + 2 * P4) % 16) / 4;     // AA: [x ; Rx ; L]
-  static constexpr int FS = (2 * P4) / 16, TS = ((2 * P4) % 16) / 4;             // S and AN: [L ; Nx]
-  static constexpr int FN = P4 / 16, TN = (P4 % 16) / 4;                         // NN: [L]
-  static constexpr int NREG = 4 * FA + TA + 2 * (4 * FS + TS) + 4 * FN + TN;     // A-operand registers per lane
-  static constexpr int SUB = 1;                                 // 16-item sub-tiles per buffer = per workgroup barrier (2: no faster, and the
-                                                                // pending-candidate buffers below need the LDS for three workgroups per CU)
-  static constexpr int TILE_F4 = SUB * IBT * ROW4 + 4;          // + pad: the padded K blocks read a little past the last row
-#ifndef KTUP_EVAL_MINW3
-#define KTUP_EVAL_MINW3 3
-#endif
-  static constexpr int MINW = NREG <= 64 ? KTUP_EVAL_MINW3 : 2;                 // waves per SIMD the register budget allows (= workgroups per CU)
-};
+// QGeom, the A-operand load, the tile DMA, the MFMA chain and the score formula: ktup_pref_q_tile.h (shared with the rank pass,
+// ktup_pref_rank_pass.hip)
 
 struct QArgs {
   const float *A, *SCU;          // users: AROW floats + 4 scalars each
@@ -171,8 +129,7 @@ struct QArgs {
 template <typename G, int SEG = 1>
 __global__ __launch_bounds__(256, (q_wgs<G, SEG>())) void eval_pass_q_kernel(QArgs a) {
   static_assert(SEG == 1 || SEG == 2 || SEG == 4, "a list is one, two or four 16-key segments");
-  constexpr int RB4 = G::RB4, ROW4 = G::ROW4, KA = G::KA, KS = G::KS, DPW = G::DPW;
-  constexpr int FA = G::FA, TA = G::TA, FS = G::FS, TS = G::TS, FN = G::FN, TN = G::TN;
+  constexpr int RB4 = G::RB4, ROW4 = G::ROW4;
   static_assert(G::SUB == 1, "one 16-item tile per buffer");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   v4* Xb = reinterpret_cast<v4*>(smem);                                   // [2][TILE_F4] item tiles
@@ -254,27 +211,7 @@ __global__ __launch_bounds__(256, (q_wgs<G, SEG>())) void eval_pass_q_kernel(QAr
   if (lane < 16) *reinterpret_cast<v4*>(usc + lane * 4) =
       u0 + lane < a.nq ? *reinterpret_cast<const v4*>(a.SCU + (u0 + lane) * 4) : (v4){0.f, 0.f, 0.f, 0.f};
   // A operands of the whole pass (user j): k-quad kq of every whole 16-block, then element kq of every remaining k-quad
-  v4 aAA[FA > 0 ? FA : 1], aS[FS > 0 ? FS : 1], aAN[FS > 0 ? FS : 1], aNN[FN > 0 ? FN : 1];
-  float tAA[TA > 0 ? TA : 1], tS[TS > 0 ? TS : 1], tAN[TS > 0 ? TS : 1], tNN[TN > 0 ? TN : 1];
-  {
-    const bool ok = u0 + j < a.nq && !(a.dbg & 32);
-    const float* rf = a.A + (ok ? u0 + j : 0) * G::AROW;
-    const v4* r0 = reinterpret_cast<const v4*>(rf);
-    constexpr int oS = 16 * KA, oAN = oS + 16 * KS, oNN = oAN + 16 * KS;
-    const v4 z4 = (v4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int g = 0; g < FA; ++g) aAA[g] = ok ? r0[4 * g + kq] : z4;
-#pragma unroll
-    for (int m = 0; m < TA; ++m) tAA[m] = ok ? rf[16 * FA + 4 * m + kq] : 0.f;
-#pragma unroll
-    for (int g = 0; g < FS; ++g) { aS[g] = ok ? r0[oS / 4 + 4 * g + kq] : z4; aAN[g] = ok ? r0[oAN / 4 + 4 * g + kq] : z4; }
-#pragma unroll
-    for (int m = 0; m < TS; ++m) { tS[m] = ok ? rf[oS + 16 * FS + 4 * m + kq] : 0.f; tAN[m] = ok ? rf[oAN + 16 * FS + 4 * m + kq] : 0.f; }
-#pragma unroll
-    for (int g = 0; g < FN; ++g) aNN[g] = ok ? r0[oNN / 4 + 4 * g + kq] : z4;
-#pragma unroll
-    for (int m = 0; m < TN; ++m) tNN[m] = ok ? rf[oNN + 16 * FN + 4 * m + kq] : 0.f;
-  }
+  KTUP_Q_USER_OPS(G, u0 + j < a.nq && !(a.dbg & 32), a.A + (ok ? u0 + j : 0) * G::AROW, kq)
   if (use_bmg) {
     const int nw = 16 * a.bm_words;
 #pragma unroll
@@ -289,29 +226,9 @@ __global__ __launch_bounds__(256, (q_wgs<G, SEG>())) void eval_pass_q_kernel(QAr
   const int64_t ntile = (a.dbg & 8) ? 0 : (i_hi - i_lo + IBT - 1) / IBT;    // (dbg 8: prologue and epilogue only)
   // this lane's float4 of every DMA piece of its wave: byte offset inside a tile (tiles past the table's end re-read its last row:
   // their items are masked out below, the operands only have to be finite)
-  uint32_t soff[DPW];
-#pragma unroll
-  for (int k = 0; k < DPW; ++k) {
-    const int slot = 64 * (w + 4 * k) + lane;
-    soff[k] = slot < G::TSLOTS ? (uint32_t)slot * 16u : 0xffffffffu;
-  }
+  KTUP_Q_DMA_OFFSETS(G, soff, w, lane)
   auto dma = [&](int64_t t, int buf) {                                    // tile t of this split -> LDS buffer `buf`
-    const int64_t row0 = i_lo + t * IBT;
-    const char* src = reinterpret_cast<const char*>(a.B + row0 * G::GROW);
-    v4* dst = Xb + buf * G::TILE_F4 + 64 * w;
-    const bool tail = row0 + IBT > a.n_items;                             // (uniform)
-#pragma unroll
-    for (int k = 0; k < DPW; ++k) {
-      if (soff[k] == 0xffffffffu) continue;
-      const char* from = src + soff[k];
-      if (tail) {
-        const uint32_t slot = soff[k] >> 4, row = slot / ROW4, c = slot - row * ROW4;
-        const int64_t r = row0 + row < a.n_items ? row0 + row : a.n_items - 1;
-        from = reinterpret_cast<const char*>(a.B + r * G::GROW + 4 * c);
-      }
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)from,
-                                       (__attribute__((address_space(3))) void*)(dst + 256 * k), 16, 0, 0);
-    }
+    KTUP_Q_TILE_DMA(G, a.B, a.n_items, i_lo + t * IBT, Xb + buf * G::TILE_F4 + 64 * w, soff)
   };
   const int rowbase = 16 * kq;
   // A user's list is touched only when 16 candidates are pending for it.  A score is a candidate if it is below the user's n-th score
@@ -375,50 +292,7 @@ __global__ __launch_bounds__(256, (q_wgs<G, SEG>())) void eval_pass_q_kernel(QAr
     __builtin_amdgcn_wave_barrier();
   };
   auto compute = [&](int buf, int sub, int64_t t, const int (&gl)[4]) {   // 16 users x the 16 items of tile t
-    const v4* ib = Xb + buf * G::TILE_F4 + (sub * IBT + j) * ROW4 + kq;   // lane (kq, item j): k-quad kq of every 16-block
-    v4 accAA = (v4){0.f, 0.f, 0.f, 0.f}, accS = accAA, accAN = accAA, accNN = accAA;
-    // B operands one step ahead of the MFMAs that use them (two register sets): left to itself the compiler re-uses ONE set and
-    // every group of MFMAs waits out an LDS round trip (measured: the MFMAs + reads alone took 120 us of a 68 us pipe time).
-    // Steps: AA's whole blocks, AA's remaining quads, the [L ; Nx] blocks (S, AN and -- the first FN -- NN), their remaining quads
-    // (S, AN), NN's remaining quads.
-    const float* ibf = reinterpret_cast<const float*>(Xb + buf * G::TILE_F4 + (sub * IBT + j) * ROW4) + kq;   // element kq of a k-quad
-    constexpr int S0 = FA, S1 = S0 + TA, S2 = S1 + FS, S3 = S2 + TS, NSTEP = S3 + TN;
-    constexpr int SF = 4 * G::SOFF4;                                       // float offset of [L ; Nx] inside a row
-    auto bsrc = [&](int s) -> v4 {
-      if (s < S0) return ib[4 * s];
-      if (s < S1) return (v4){ibf[16 * FA + 4 * (s - S0)], 0.f, 0.f, 0.f};
-      if (s < S2) return ib[G::SOFF4 + 4 * (s - S1)];
-      if (s < S3) return (v4){ibf[SF + 16 * FS + 4 * (s - S2)], 0.f, 0.f, 0.f};
-      return (v4){ibf[SF + 16 * FN + 4 * (s - S3)], 0.f, 0.f, 0.f};
-    };
-    v4 bcur = bsrc(0);
-#pragma unroll
-    for (int s = 0; s < NSTEP; ++s) {
-      v4 bnext = bcur;
-      if (s + 1 < NSTEP) bnext = bsrc(s + 1);
-      __builtin_amdgcn_sched_barrier(0);                                   // the read stays ahead of the MFMAs below
-      if (s < S0) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) accAA = __builtin_amdgcn_mfma_f32_16x16x4f32(aAA[s][c], bcur[c], accAA, 0, 0, 0);
-      } else if (s < S1) {
-        accAA = __builtin_amdgcn_mfma_f32_16x16x4f32(tAA[s - S0], bcur[0], accAA, 0, 0, 0);
-      } else if (s < S2) {
-        const int g = s - S1;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          accS = __builtin_amdgcn_mfma_f32_16x16x4f32(aS[g][c], bcur[c], accS, 0, 0, 0);
-          accAN = __builtin_amdgcn_mfma_f32_16x16x4f32(aAN[g][c], bcur[c], accAN, 0, 0, 0);
-          if (g < FN) accNN = __builtin_amdgcn_mfma_f32_16x16x4f32(aNN[g][c], bcur[c], accNN, 0, 0, 0);
-        }
-      } else if (s < S3) {
-        accS = __builtin_amdgcn_mfma_f32_16x16x4f32(tS[s - S2], bcur[0], accS, 0, 0, 0);
-        accAN = __builtin_amdgcn_mfma_f32_16x16x4f32(tAN[s - S2], bcur[0], accAN, 0, 0, 0);
-      } else {
-        accNN = __builtin_amdgcn_mfma_f32_16x16x4f32(tNN[s - S3], bcur[0], accNN, 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      bcur = bnext;
-    }
+    KTUP_Q_TILE_MFMA(G, Xb + buf * G::TILE_F4 + (sub * IBT + j) * ROW4, kq)   // lane (kq, item j) -> accAA, accS, accAN, accNN
     const v4 is4 = Xb[buf * G::TILE_F4 + (sub * IBT + j) * ROW4 + RB4];      // the row's scalars ride in its tile slot
     const int64_t item = i_lo + t * IBT + j;
     const int64_t lid = item - i_lo;
@@ -435,11 +309,7 @@ __global__ __launch_bounds__(256, (q_wgs<G, SEG>())) void eval_pass_q_kernel(QAr
       //  either sign keeps the meaning it has without the shared word)
       thrf[reg] = __int_as_float(min(__float_as_int(thrf[reg]), gl[reg]));
       const v4 us4 = *reinterpret_cast<const v4*>(usc + ur * 4);
-      const float sv = (us4[0] + accS[reg]) - is4[0];
-      const float aa = (us4[1] + is4[1]) + accAA[reg];
-      const float an = (us4[2] + accAN[reg]) - is4[2];
-      const float nn = (us4[3] + is4[3]) + accNN[reg];
-      const float score = fmaf(sv * sv, nn, fmaf(-2.f * sv, an, aa));
+      const float score = q_score(us4, is4, accS[reg], accAA[reg], accAN[reg], accNN[reg]);
       // one compare whose result stays a wave mask; with the shared bounds many 64-score slots have no candidate and leave here
       const uint64_t m_ngt = __builtin_amdgcn_ballot_w64(!(score > thrf[reg]));   // below the bound, equal to it, or unordered
       if (m_ngt == 0) continue;
@@ -897,6 +767,57 @@ QScratch q_carve(void* scratch, int64_t nq, int64_t n_items, size_t part_keys) {
   return s;
 }
 
+// The operand tables of a pass, for the list passes (launch_q) and the rank pass (pref_q_tables below; ktup_pref_rank_pass.hip): the
+// Gram launch and the operand-row launch, with the filter bitmap's waves riding in one of them where the caller has one (use_bm; fb
+// always names the Gram workgroups).  ONE rule for rows_mc -- the two row kernels round differently, and the ranks are counts against
+// the list pass's own bits.  gthr: the users' shared bounds the row launch resets (NULL: none).
+// The two row kernels come as ARGUMENTS (q_row_kernels<G>() at the call): a translation unit's kernels are emitted in the order its
+// host code first names them, and launch_q names them before its sweep kernel as it did when these launches stood in its own body
+// -- so the object's kernels keep their order and the file compares equal line by line (profiles/pref_ranks_narrow_check.txt).
+using RowsMcKernel = void (*)(RowsSide, RowsSide, int, const float*, const float*, const float*, int, const float*, int, int, FiltBm);
+using RowsKernel = void (*)(RowsSide, RowsSide, int, const float*, const float*, const float*, int, const float*, int, int);
+struct RowKernels { RowsMcKernel mc; RowsKernel row; };                 // mc == NULL: no matrix-core row kernel at this geometry
+// d = 256: the three staged tables + the Gram operands + four wave tiles of the matrix-core row kernel pass the LDS of a CU at P > 4
+// (RGeom<64, 5>::LDS = 176 KB, <64, 8> 182 KB; <64, 1> 118 KB fits): those take the one-wave-per-row kernel, which stages nothing
+template <typename G>
+RowKernels q_row_kernels() {
+  RowKernels k{nullptr, nullptr};
+  if constexpr (RGeom<G::NCH, G::NP>::LDS <= 160 * 1024) k.mc = pspace_rows_mc_kernel<G::NCH, G::NP>;
+  k.row = pspace_rows_kernel<G::NCH, G::NP>;
+  return k;
+}
+
+template <typename G>
+int q_tables(const RowKernels& kern, const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, const float* I, int64_t ldi, const float* E,
+             int64_t lde, const int32_t* item2ent, int64_t n_items, const float* pref_ws, int ppad, int dp, int n_pref, const QScratch& q,
+             int32_t* gthr, const FiltBm& fb, bool use_bm, size_t bm_lds, hipStream_t st, const char* name) {
+  const float* Alog = pref_ws;
+  const float* Ar = pref_ws + (size_t)ppad * dp;
+  const float* Cn = pref_ws + (size_t)(ppad + n_pref) * dp;
+  using R = RGeom<G::NCH, G::NP>;
+  const bool rows_mc = kern.mc && opt_eval_mc() && !((ldu | ldi | lde | dp) & 3) && aligned16(U) && aligned16(I) && (!E || aligned16(E)) &&
+                       aligned16(pref_ws) && nq < (1ll << 31) && n_items < (1ll << 31);
+  const int64_t ublocks = (nq + 63) / 64;
+  // the bitmap's waves ride in the operand-row launch (16 us, 146 workgroups at ml1m size); without the matrix-core row kernel, in the Gram launch
+  const bool bm_in_gram = use_bm && !rows_mc;
+  hipLaunchKernelGGL(pspace_gram_kernel, dim3(fb.gram_blocks + (bm_in_gram ? (unsigned)ublocks : 0u)), dim3(256), bm_in_gram ? bm_lds : 0, st, Ar, Cn, dp,
+                     G::D, n_pref, G::P4, q.grams, rows_mc ? q.gs : nullptr, R::PT, G::NP, fb);
+  const size_t lds_rows = (size_t)4 * (G::D + 7 * G::P4) * sizeof(float);
+  // many small workgroups: a row is a chain of dependent round trips (id -> row -> products -> store), hidden only by occupancy
+  RowsSide us{U, ldu, u_ids, nullptr, 0, nullptr, nq, q.A, G::AROW, q.SCU, grid_for((nq + 3) / 4, 2048), G::AROW, 4, gthr};
+  RowsSide is{I, ldi, nullptr, E, lde, item2ent, n_items, q.B, G::ROWB, q.B + G::ROWB, grid_for((n_items + 3) / 4, 2048), G::GROW, G::GROW, nullptr};
+  if (rows_mc) {    // 16 rows per wave on the matrix cores
+    us.blocks = (int)((nq + 63) / 64); is.blocks = (int)((n_items + 63) / 64);
+    const size_t rows_lds = use_bm && bm_lds > R::LDS ? bm_lds : R::LDS;
+    (void)hipFuncSetAttribute((const void*)kern.mc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds);
+    hipLaunchKernelGGL(kern.mc, dim3(us.blocks + is.blocks + (use_bm ? (unsigned)ublocks : 0u)), dim3(256), rows_lds, st, us, is, n_pref, Alog, Ar, Cn,
+                       dp, q.gs, G::KA, G::KS, fb);
+  } else {
+    hipLaunchKernelGGL(kern.row, dim3(us.blocks + is.blocks), dim3(256), lds_rows, st, us, is, n_pref, Alog, Ar, Cn, dp, q.grams, G::KA, G::KS);
+  }
+  return check_launch(name);
+}
+
 // SEG = 1: the narrow entry point's pass.  SEG = 2, 4: the wide one's (topn <= 16 SEG).
 template <typename G, int SEG = 1>
 int launch_q(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, const float* I, int64_t ldi, const float* E, int64_t lde,
@@ -905,15 +826,6 @@ int launch_q(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, cons
              float* top_scores, hipStream_t st, const char* name) {
   constexpr bool WIDE = SEG > 1;
   const QScratch q = q_carve<G>(scratch, nq, n_items, q_part_keys(topn, WIDE));
-  const float* Alog = pref_ws;
-  const float* Ar = pref_ws + (size_t)ppad * dp;
-  const float* Cn = pref_ws + (size_t)(ppad + n_pref) * dp;
-  using R = RGeom<G::NCH, G::NP>;
-  // d = 256: the three staged tables + the Gram operands + four wave tiles of the matrix-core row kernel pass the LDS of a CU at P > 4
-  // (RGeom<64, 5>::LDS = 176 KB, <64, 8> 182 KB; <64, 1> 118 KB fits): those take the one-wave-per-row kernel, which stages nothing
-  constexpr bool ROWS_MC_FITS = R::LDS <= 160 * 1024;
-  const bool rows_mc = ROWS_MC_FITS && opt_eval_mc() && !((ldu | ldi | lde | dp) & 3) && aligned16(U) && aligned16(I) && (!E || aligned16(E)) &&
-                       aligned16(pref_ws) && nq < (1ll << 31) && n_items < (1ll << 31);
   // the catalogue splits of the sweep (decided here: the filter bitmap is laid out by split)
   const int64_t ublocks = (nq + 63) / 64;
   const int max_splits = q_max_splits(topn, WIDE);
@@ -948,27 +860,8 @@ int launch_q(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, cons
   const bool use_bm = filt_off && filt_ids && filt_bm_bytes(nq, n_items) && (size_t)nsplit * bm_words <= filt_bm_words_per_user(n_items) &&
                       bm_lds <= 64 * 1024;
   FiltBm fb{filt_off, filt_ids, nq, n_items, q.bm, nsplit, bm_words, (uint32_t)split_items, gram_blocks};
-  // the bitmap's waves ride in the operand-row launch (16 us, 146 workgroups at ml1m size); without the matrix-core row kernel, in the Gram launch
-  const bool bm_in_gram = use_bm && !rows_mc;
-  hipLaunchKernelGGL(pspace_gram_kernel, dim3(gram_blocks + (bm_in_gram ? (unsigned)ublocks : 0u)), dim3(256), bm_in_gram ? bm_lds : 0, st, Ar, Cn, dp,
-                     G::D, n_pref, G::P4, q.grams, rows_mc ? q.gs : nullptr, R::PT, G::NP, fb);
-  const size_t lds_rows = (size_t)4 * (G::D + 7 * G::P4) * sizeof(float);
-  // many small workgroups: a row is a chain of dependent round trips (id -> row -> products -> store), hidden only by occupancy
-  RowsSide us{U, ldu, u_ids, nullptr, 0, nullptr, nq, q.A, G::AROW, q.SCU, grid_for((nq + 3) / 4, 2048), G::AROW, 4, q.gthr};
-  RowsSide is{I, ldi, nullptr, E, lde, item2ent, n_items, q.B, G::ROWB, q.B + G::ROWB, grid_for((n_items + 3) / 4, 2048), G::GROW, G::GROW, nullptr};
-  if (rows_mc) {    // 16 rows per wave on the matrix cores
-    if constexpr (ROWS_MC_FITS) {
-      us.blocks = (int)((nq + 63) / 64); is.blocks = (int)((n_items + 63) / 64);
-      const size_t rows_lds = use_bm && bm_lds > R::LDS ? bm_lds : R::LDS;
-      (void)hipFuncSetAttribute((const void*)pspace_rows_mc_kernel<G::NCH, G::NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_lds);
-      hipLaunchKernelGGL((pspace_rows_mc_kernel<G::NCH, G::NP>), dim3(us.blocks + is.blocks + (use_bm ? (unsigned)ublocks : 0u)), dim3(256), rows_lds, st,
-                         us, is, n_pref, Alog, Ar, Cn, dp, q.gs, G::KA, G::KS, fb);
-    }
-  } else {
-    hipLaunchKernelGGL((pspace_rows_kernel<G::NCH, G::NP>), dim3(us.blocks + is.blocks), dim3(256), lds_rows, st, us, is, n_pref, Alog, Ar, Cn, dp,
-                       q.grams, G::KA, G::KS);
-  }
-  if (int e = check_launch(name)) return e;
+  if (int e = q_tables<G>(q_row_kernels<G>(), U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, n_pref, q, q.gthr, fb, use_bm, bm_lds, st, name))
+    return e;
   QArgs a{};
   a.A = q.A; a.SCU = q.SCU; a.B = q.B; a.nq = nq; a.n_items = n_items;
   a.filt_off = filt_off; a.filt_ids = filt_ids; a.topn = topn; a.part = q.part; a.dbg = opt_dbg_eval();
@@ -978,6 +871,18 @@ int launch_q(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, cons
   hipLaunchKernelGGL((eval_pass_q_kernel<G, SEG>), dim3((unsigned)ublocks, (unsigned)nsplit), dim3(256), lds, st, a);
   if (int e = check_launch(name)) return e;
   return launch_topk_merge(q.part, nq, nsplit, topn, WIDE, top_ids, top_scores, st, name);   // nsplit x topn <= 128 (narrow) / 512 keys per user
+}
+
+// the rank pass's tables: Gram matrices and operand rows in the head of the list pass's scratch layout, no partial lists, bounds or bitmap
+template <typename G>
+int q_tables_only(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, const float* I, int64_t ldi, const float* E, int64_t lde,
+                  const int32_t* item2ent, int64_t n_items, const float* pref_ws, int ppad, int dp, int n_pref, void* scratch, PrefQTables* out,
+                  hipStream_t st, const char* name) {
+  const QScratch q = q_carve<G>(scratch, nq, n_items, 0);
+  const FiltBm fb{nullptr, nullptr, nq, n_items, nullptr, 1, 0, 0u, (3 * G::P4 * G::P4 + 3) / 4};
+  out->A = q.A; out->SCU = q.SCU; out->B = q.B;
+  return q_tables<G>(q_row_kernels<G>(), U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, n_pref, q, nullptr, fb, false, 0, st,
+                     name);
 }
 
 template <int NCH, int SEG>
@@ -1045,6 +950,31 @@ int eval_pass_pspace(const float* U, int64_t ldu, const int64_t* u_ids, int64_t 
   if (!wide) return launch_q_d<1>(d, n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
   if (topn <= 32) return launch_q_d<2>(d, n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
   return launch_q_d<4>(d, n_pref, U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, filt_off, filt_ids, topn, scratch, top_ids, top_scores, st, name);
+}
+
+// The operand tables alone, for the rank pass (ktup_pref_rank_pass.hip; defined after the list passes' entry so that their kernels are
+// named first): `scratch` of pref_q_tables_bytes bytes, 16-byte aligned; *out:
+// where the user rows, their scalars and the item rows are.  d in {64, 100, 128}, 1 <= n_pref <= 32 (the caller checked).
+size_t pref_q_tables_bytes(int d, int n_pref, int64_t nq, int64_t n_items) {
+  const size_t p4 = n_pref <= 4 ? 4 : n_pref <= 20 ? 20 : 32;
+  const size_t ka = (d + 2 * p4 + 15) / 16, ks = (2 * p4 + 15) / 16, kn = (p4 + 15) / 16;
+  const size_t arow = 16 * (ka + 2 * ks + kn), rowb = d + 3 * p4, grow = 4 * ((rowb / 4 + 1) | 1);      // QGeom::AROW, ROWB, GROW
+  return (3 * 32 * 32 + 4 * 2 * 8 * 64 + (size_t)nq * (arow + 4) + (size_t)n_items * grow + 64) * sizeof(float);
+}
+int pref_q_tables(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, const float* I, int64_t ldi, const float* E, int64_t lde,
+                  const int32_t* item2ent, int64_t n_items, const float* pref_ws, int ppad, int dp, int n_pref, int d, void* scratch,
+                  PrefQTables* out, hipStream_t st, const char* name) {
+  auto by_p = [&](auto nch) {
+    constexpr int NCH = decltype(nch)::value;
+    if (n_pref <= 4)
+      return q_tables_only<QGeom<NCH, 1>>(U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, n_pref, scratch, out, st, name);
+    if (n_pref <= 20)
+      return q_tables_only<QGeom<NCH, 5>>(U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, n_pref, scratch, out, st, name);
+    return q_tables_only<QGeom<NCH, 8>>(U, ldu, u_ids, nq, I, ldi, E, lde, item2ent, n_items, pref_ws, ppad, dp, n_pref, scratch, out, st, name);
+  };
+  if (d == 64) return by_p(std::integral_constant<int, 16>{});
+  if (d == 100) return by_p(std::integral_constant<int, 25>{});
+  return by_p(std::integral_constant<int, 32>{});
 }
 
 }  // namespace ktup

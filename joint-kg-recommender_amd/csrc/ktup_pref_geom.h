@@ -109,6 +109,13 @@ int eval_pass_pspace(const float* U, int64_t ldu, const int64_t* u_ids, int64_t 
                      const int32_t* item2ent, int64_t n_items, const float* pref_ws,
                      int ppad, int dp, int n_pref, int d, const int64_t* filt_off, const int32_t* filt_ids, int topn, void* scratch,
                      int32_t* top_ids, float* top_scores, hipStream_t st, const char* name, bool wide = false);
+// ktup_eval_pass.hip: the operand tables of that pass alone (Gram, operand-row launches; the list pass's own rule for the row kernel),
+// for the rank pass (ktup_pref_rank_pass.hip).  d in {64, 100, 128}, 1 <= n_pref <= 32.
+struct PrefQTables { const float *A, *SCU, *B; };   // user rows (QGeom::AROW floats), their 4 scalars, item rows (QGeom::GROW floats)
+size_t pref_q_tables_bytes(int d, int n_pref, int64_t nq, int64_t n_items);
+int pref_q_tables(const float* U, int64_t ldu, const int64_t* u_ids, int64_t nq, const float* I, int64_t ldi, const float* E, int64_t lde,
+                  const int32_t* item2ent, int64_t n_items, const float* pref_ws, int ppad, int dp, int n_pref, int d, void* scratch,
+                  PrefQTables* out, hipStream_t st, const char* name);
 int pairs_kg_l2_mc(int model, const float* QW, int dq, const float* C, int64_t ldc, int d, int64_t nq, int64_t n_cand, float* out,
                    int64_t ldo, hipStream_t st, const char* name, const float* qcc = nullptr,
                    const float* cnorm = nullptr, const int32_t* qrel = nullptr);

@@ -200,6 +200,10 @@ SIGNATURES = {
     'ktup_eval_cfkg_ranks_workspace_bytes': [c_i, c_l, c_l, c_l, c_l],
     'ktup_eval_cfkg_ranks': [c_p, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_l, c_l, c_i, c_p, c_p,
                              c_p],
+    'ktup_eval_pref_ranks_supported': [c_i, c_i, c_i, c_l, c_l],
+    'ktup_eval_pref_ranks_workspace_bytes': [c_i, c_i, c_i, c_l, c_l, c_l, c_l],
+    'ktup_eval_pref_ranks': [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_p, c_i, c_i, c_p, c_l, c_l, c_i, c_p, c_p, c_p, c_p, c_l, c_l, c_i, c_p, c_p,
+                             c_p],
     'ktup_eval_kg_ranks_transr_fused_supported': [c_i, c_i, c_l],
     'ktup_eval_kg_ranks_transr_fused_workspace_bytes': [c_i, c_l, c_l, c_l, c_l, c_i],
     'ktup_eval_kg_ranks_transr_fused': [c_p, c_l, c_p, c_l, c_p, c_l, c_i, c_l, c_i, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_l,
@@ -222,6 +226,7 @@ _RESTYPE = {'ktup_last_error': ctypes.c_char_p, 'ktup_shard_reduce_list_len': ct
             'ktup_eval_cfkg_topk_workspace_bytes': ctypes.c_size_t, 'ktup_eval_dot_topk_wide_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_cfkg_topk_wide_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_dot_ranks_workspace_bytes': ctypes.c_size_t, 'ktup_eval_cfkg_ranks_workspace_bytes': ctypes.c_size_t,
+            'ktup_eval_pref_ranks_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_pref_topk_wide_workspace_bytes': ctypes.c_size_t, 'ktup_eval_pref_topk_hard_wide_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_kg_ranks_transd_fused_workspace_bytes': ctypes.c_size_t,
             'ktup_eval_kg_ranks_transr_fused_workspace_bytes': ctypes.c_size_t,

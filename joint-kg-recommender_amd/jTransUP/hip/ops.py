@@ -1202,9 +1202,11 @@ def _block_golds(gold_off):
     return hit[1]
 
 
-def _rank_sweep(entry, who, head, tail, d, nq, n, gold_off, gold_ids, filt_off, filt_ids, nsplit, dev):
+def _rank_sweep(entry, who, head, tail, d, nq, n, gold_off, gold_ids, filt_off, filt_ids, nsplit, dev, shape=None):
     """The tail of the one-sweep gold-rank wrappers: entry(*head, u, nq, *tail, filters, golds, n_gold, block_golds, nsplit, ranks,
-    workspace, stream) -> int32 [n_gold]; None where the entry point declines the shape."""
+    workspace, stream) -> int32 [n_gold]; None where the entry point declines the shape.  `shape`: what _supported and
+    _workspace_bytes take in front of their sizes ((d,) unless given)."""
+    shape = (d,) if shape is None else shape
     filt_off, filt_ids = _no_empty_filter(filt_off, filt_ids)
     _csr_offsets(who, nq, gold_off, filt_off)
     if gold_ids.dtype != torch.int32 or gold_off.dtype != torch.int64 or gold_ids.device != dev or gold_off.device != dev:
@@ -1217,9 +1219,9 @@ def _rank_sweep(entry, who, head, tail, d, nq, n, gold_off, gold_ids, filt_off, 
         return None
     lib = L.load()
     bg = _block_golds(gold_off)
-    if not getattr(lib, entry + '_supported')(d, n, bg):
+    if not getattr(lib, entry + '_supported')(*shape, n, bg):
         return None
-    ws = _scratch(getattr(lib, entry + '_workspace_bytes')(d, nq, n, n_gold, bg), dev)
+    ws = _scratch(getattr(lib, entry + '_workspace_bytes')(*shape, nq, n, n_gold, bg), dev)
     try:
         L.call(entry, *head, nq, *tail, _p(filt_off), _p(filt_ids), _p(gold_off), _p(gold_ids), n_gold, bg, int(nsplit), _p(ranks), _p(ws),
                _stream(dev))
@@ -1272,6 +1274,29 @@ def eval_cfkg_ranks(U, R, rel, E, u, l1, gold_off, gold_ids, cand_ids=None, filt
     head = (_p(U), U.stride(0), _p(R), R.stride(0), int(rel), _p(E), E.stride(0), ne, _p(cand_ids), nc, d, _p(u))
     return _rank_sweep('ktup_eval_cfkg_ranks', 'eval_cfkg_ranks', head, (int(bool(l1)),), d, nq, nc, gold_off, gold_ids, filt_off, filt_ids, nsplit,
                        dev)
+
+
+@torch.no_grad()
+def eval_pref_ranks(U, u, items, l1, gold_off, gold_ids, filt_off=None, filt_ids=None, nsplit=0):
+    """The filtered rank of every gold item of a whole TUP / KTUP evaluation pass in one sweep (ktup_eval_pref_ranks): gold_ranks(
+    descending=False) on the scores of eval_pref_topk's preference-space pass -- the same bits, no (users x items) matrix.  `items`:
+    eval_pref_items(...) of the current tables; gold_off: int64 (len(u) + 1,) absolute offsets into gold_ids (int32), per user of `u`.
+    -> int32 [len(gold_ids)], -1 for a gold that is filtered or outside the catalogue; None where the pass declines: L1, a width other
+    than 64 / 100 / 128 (256 too, whatever option eval_q256 says), more than 32 preferences, option eval_mc = 0, a 64-user block with
+    more gold entries than its LDS holds -- keep the matrix route.  One device read per CSR index (the largest block), none after:
+    the call can be captured in a graph."""
+    U, u = _pad_users(U, u)
+    dev = _dev(_table('user table', U))
+    u = _ids('u_ids', u, dev)
+    nq, d, P = u.numel(), items.d, items.P
+    if U.shape[1] != d or items.I.device != dev:
+        raise L.KtupError('the user table and the prepared item side must share the device and the embedding size')
+    if d == 256 or not pref_pass_covers(items, l1) or P > 32:
+        return None
+    I, E = items.I, items.E
+    head = (_p(U), U.stride(0), _p(I), I.stride(0), _p(E), 0 if E is None else E.stride(0), _p(items.item2ent), _p(items.pws), P, d, _p(u))
+    return _rank_sweep('ktup_eval_pref_ranks', 'eval_pref_ranks', head, (items.n_items, 0), d, nq, items.n_items, gold_off, gold_ids, filt_off,
+                       filt_ids, nsplit, dev, shape=(d, P, 0))
 
 
 TOPN_MAX, TOPN_WIDE_MAX = 16, 64       # csrc/ktup_topn.h: one key per lane of a 16-lane row; up to four such segments

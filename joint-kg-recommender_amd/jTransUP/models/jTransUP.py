@@ -131,6 +131,17 @@ class jTransUPModel(nn.Module, GradToggle, GateHelpers):
             return None
         return sweep(self.user_embeddings.weight, u_ids, items, self.L1_flag, topn, filt_off, filt_ids, model_call=True)
 
+    def rank_items(self, u_ids, items, gold_off, gold_ids, filt_off=None, filt_ids=None):
+        """The filtered rank of every gold item of every user of `u_ids` in one sweep (ops.eval_pref_ranks): gold_ranks on the scores
+        of evaluate_topk's preference-space pass, ascending, without the (users x items) matrix.  `items`: `prepare_items()` (None:
+        taken here).  -> int32 [len(gold_ids)], -1 for a gold that is itself filtered; None under the ST-Gumbel gate and where the
+        sweep declines (L1, a width other than 64 / 100 / 128, more than 32 preferences): the caller keeps the matrix route."""
+        if self.use_st_gumbel:
+            return None
+        if items is None:
+            items = self.prepare_items()
+        return ops.eval_pref_ranks(self.user_embeddings.weight, u_ids, items, self.L1_flag, gold_off, gold_ids, filt_off, filt_ids)
+
     def prepare_items(self, all_i_ids=None):
         """Item side of `evaluateRec` (item + entity rows through the preference gate), to share between the batches of a pass."""
         _, _, E, P, Pn, R, Rn = self._rec_tables()

@@ -86,7 +86,8 @@ def evaluateRec(FLAGS, model, eval_iter, eval_dict, all_dicts, i_map, logger, ev
                                   pass_descending=getattr(model, 'topk_descending', False))
     perf = D.summarize_rec(FLAGS, results, logger)
     # KTUP_REC_RANKS=1: MRR, mean rank and AUC of the same users on a line of their own.  model.rank_items' sweep where evaluate_topk's
-    # would serve (own item table, or CFKG's entity-row candidates), the batch walk otherwise (TUP / KTUP, -share_embeddings)
+    # would serve (own item table -- KTUP's preference-space pass included --, or CFKG's entity-row candidates), the batch walk
+    # otherwise (-share_embeddings, and where rank_items answers None: the ST-Gumbel gate, L1, widths other than 64 / 100 / 128)
     rank_fn = None
     if hasattr(model, 'rank_items') and not FLAGS.share_embeddings:
         rank_fn = lambda u, go, gi, fo, fi: model.rank_items(u, None, go, gi, fo, fi)
